@@ -10,6 +10,11 @@ tokens) + guidance combine + FlowMatch-Euler update, weights random-initialised 
 checkpoints offline), everything resident in HBM when the clock starts.  With N > 1 every rank
 denoises its own sample (replicas; the path has no exchange step), so
 value = N*K / max-over-ranks time ("weak" scaling).
+
+A plain run builds the model, runs W untimed and K timed steps and prints the headline line (value,
+ms_per_step); --dump-outputs DIR also writes the latents after the last step as DIR/latents.npy.
+--full adds the instrumented measurements: per-kernel roofline of the timed steps, clock / power,
+the text-only and cached-adapter legs and the CPU baseline.
 """
 import argparse
 import json
@@ -109,6 +114,24 @@ def _make_conditions(dev, seed, w, n_time_ids, text_dim=4096, pooled_dim=2048):
         crossview_attention_mask=ring[None].repeat(B2, 1, 1).to(dev),
         added_time_ids=torch.rand(B2, T, V, n_time_ids, device=dev, generator=g) * 2 - 1,
     )
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, outputs: dict, rank: int = 0):
+    """--dump-outputs: each tensor of `outputs` as <out_dir>/<name>.npy in float32 (rank 0 writes; the caller gathers a
+    frame-sharded result first).  The headline's latents are 6.9 MB; more than DUMP_LIMIT_BYTES in all is an error."""
+    import numpy as np
+    arrays = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}")
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 class ClockPowerSampler:
@@ -1012,8 +1035,17 @@ def main():
                     help="with --train: freezing_pattern ^(transformer_blocks|time_text_embed)$ of the reference's warm-up configs")
     ap.add_argument("--debug-cpu-launch", action="store_true",
                     help="debug: exercise the launch / timing path on CPU over gloo with a stand-in step (INVALID as a bench line)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: per-kernel HIP-event roofline (GEMM / attention, committed PMC traffic), "
+                         "clock / power sampling during the timed steps, the text-only and cached-adapter legs, the CPU baseline.  "
+                         "Without it the headline run times its steps un-instrumented and prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the headline path returns after its last step (the denoised latents, "
+                         "float32) as DIR/<name>.npy; the inputs are seeded, so equal arguments give equal inputs")
     args = ap.parse_args()
     args.steps_given = any(a == "--steps" or a.startswith("--steps=") for a in sys.argv[1:])
+    if args.dump_outputs and (args.debug_cpu_launch or args.train or args.unet or args.tvae_ar):
+        ap.error("--dump-outputs writes the headline workload's outputs only")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
     if args.debug_cpu_launch:
@@ -1062,15 +1094,18 @@ def main():
         sample_id, n_samples = 0, 1
     ninf = w["inference_steps"]
 
-    def run_variant(layout: bool, steps: int, warmup: int, adapter_cache: bool = bool(args.adapter_cache)):
-        """build the model of one variant, W untimed + K timed denoise steps; -> (kwargs, seconds, KernelTimer, finite)"""
+    # the per-kernel HIP events (roofline, --gemm-shapes) and the clock / power sampler belong to --full: a plain run times bare steps
+    instrument = args.full or args.gemm_shapes
+
+    def run_variant(layout: bool, steps: int, warmup: int, adapter_cache: bool = bool(args.adapter_cache), dump: str = None):
+        """build the model of one variant, W untimed + K timed denoise steps; -> (kwargs, seconds, KernelTimer or None, finite)"""
         kwargs = variant_kwargs(layout)
         if args.layers is not None:
             n = args.layers
             kwargs.update(num_layers=n, dual_attention_layers=[i for i in kwargs["dual_attention_layers"] if i < n],
                           crossview_block_layers=[i for i in kwargs["crossview_block_layers"] if i < n],
                           temporal_block_layers=[i for i in kwargs["temporal_block_layers"] if i < n])
-        timer = KernelTimer().install()
+        timer = KernelTimer().install() if instrument else None
         try:
             model = build_model(kwargs, dev, seed=0)
             if args.residual_bf16:
@@ -1088,28 +1123,33 @@ def main():
             model.cache_adapter_residuals = adapter_cache     # default: the adapter runs inside every timed step
 
             def step(i):
-                timer.enabled = i >= warmup and not args.graph
+                if timer is not None:
+                    timer.enabled = i >= warmup and not args.graph
                 den.step(i % ninf)
 
-            sampler = ClockPowerSampler(dev.index or 0).start() if rank == 0 else None
+            sampler = ClockPowerSampler(dev.index or 0).start() if rank == 0 and instrument else None
             dt = D.timed_steps(step, steps, warmup, dev)
             t_end = time.perf_counter()
-            timer.enabled = False
+            if timer is not None:
+                timer.enabled = False
             if sampler is not None:
                 sampler.stop()
                 timer.clock_power = sampler.summary(t_end - dt, t_end)
             finite = bool(torch.isfinite(den.latents).all().item())
+            if dump:
+                dump_outputs(dump, {"latents": den.result()}, rank)
         finally:
-            timer.uninstall()
+            if timer is not None:
+                timer.uninstall()
         del den, model, cond, latents
         torch.cuda.empty_cache()
         return kwargs, dt, timer, finite
 
-    kwargs, dt, timer, finite = run_variant(args.layout, args.steps, args.warmup)
+    kwargs, dt, timer, finite = run_variant(args.layout, args.steps, args.warmup, dump=args.dump_outputs)
     # the other example of BASELINE config 3 (examples/ctsd_35_6views_video_generation.json, text only,
     # row-wise temporal attention, 398.98 TFLOP/step) - reported beside the headline, outside its timed region, at N=1 only
     other = None
-    if world == 1 and args.layout and not args.no_text_only_leg and not args.graph and args.layers is None:
+    if args.full and world == 1 and args.layout and not args.no_text_only_leg and not args.graph and args.layers is None:
         try:
             k2, dt2, t2, fin2 = run_variant(False, args.steps, args.warmup)
             other = (k2, dt2, t2, fin2)
@@ -1120,7 +1160,8 @@ def main():
     # every step: the model class's own default (`cache_adapter_residuals`), what a deployment would run - reported beside the
     # headline, outside its timed region, at N=1 only
     cached = None
-    if world == 1 and args.layout and not args.adapter_cache and not args.no_text_only_leg and not args.graph and args.layers is None:
+    if (args.full and world == 1 and args.layout and not args.adapter_cache and not args.no_text_only_leg and not args.graph
+            and args.layers is None):
         try:
             cached = run_variant(True, args.steps, args.warmup, adapter_cache=True)
         except Exception as e:
@@ -1129,7 +1170,7 @@ def main():
     if rank == 0:
         fl = model_flops(kwargs, 2 * w["B"], w["T"], w["V"], w["H"], w["W"], w["text_len"])
         step_flop = fl["total"] + (fl["adapter"] if args.layout and not args.adapter_cache else 0)
-        ks = timer.summary()
+        ks = timer.summary() if timer is not None else {}
         if args.gemm_shapes:
             for row in timer.shape_table():
                 print(json.dumps(row), file=sys.stderr)
@@ -1155,48 +1196,52 @@ def main():
                        "variant": ("text+layout (ImageAdapter recomputed every step, pointwise temporal)" if not args.adapter_cache else
                                    "text+layout (ImageAdapter residuals cached across steps, pointwise temporal)")
                        if args.layout else "text only (rowwise temporal, no adapter)"},
-            "roofline": {"bound": "mfma", "kernel": "every dwm_gemm_bf16 launch of the step: gemm4w_kernel (gemm_bf16_4w.hip) where it covers the "
-                                                    "launch, gemm_bf16_kernel otherwise (all epilogues; split in by_kernel)",
-                         "achieved": gm.get("tflops"), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                         "frac": (gm.get("tflops") or 0.0) / PEAK_BF16_TFLOPS, "traffic": gemm_traffic(gm.get("by_kernel")),
-                         "traffic_unit": "L2 -> fabric bytes per launch (TCC_EA request counters: FETCH_SIZE x 2 + WRITE_SIZE in separate rocprofv3 PMC "
-                                         "passes of this command, scripts/pmc_traffic.sh; each kernel's own row, launch-weighted over by_kernel).  "
-                                         "Infinity-Cache (MALL) hits are counted, so this is an UPPER bound of the HBM bytes",
-                         "by_kernel": {k: {kk: vv for kk, vv in v.items() if kk != "ms"} |
-                                       {"share_of_step_time": (v["ms"] / args.steps) / step_ms, "traffic": pmc_traffic(k),
-                                        "traffic_dram_est": pmc_dram(k), "traffic_source": pmc_traffic_file(k)}
-                                       for k, v in (gm.get("by_kernel") or {}).items()},
-                         "algorithmic_flop_per_launch": (gm.get("flops") or 0.0) / max(gm.get("launches") or 1, 1),
-                         "launches": gm.get("launches"), "avg_launch_us": gm.get("avg_us"),
-                         "share_of_step_time": (gm.get("ms", 0.0) / args.steps) / step_ms},
-            "roofline_attention": {"bound": "mfma", "kernel": "attn_stream_kernel (attention_stream.hip: one wave per SIMD, V of a head double-buffered in LDS, K fragments "
-                                                              "from global memory, Q in AGPRs with the softmax scale folded in by the q RMSNorm; joint L=602, dual L=448, "
-                                                              "row-wise temporal L=448; round 5: attn_res_kernel)",
-                                   "achieved": at.get("tflops"), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                                   "frac": (at.get("tflops") or 0.0) / PEAK_BF16_TFLOPS,
-                                   "launches": at.get("launches"), "avg_launch_us": at.get("avg_us"),
-                                   "share_of_step_time": (at.get("ms", 0.0) / args.steps) / step_ms,
-                                   "traffic": pmc_traffic("attn_stream_kernel"), "traffic_source": pmc_traffic_file("attn_stream_kernel"),
-                                   "mfma_pipe_busy": pmc_mfma_busy("attn_stream_kernel"),
-                                   "all_attention_launches_tflops": ((at.get("flops") or 0.0) + (asm.get("flops") or 0.0) + (agr.get("flops") or 0.0)) /
-                                   max((at.get("ms") or 0.0) + (asm.get("ms") or 0.0) + (agr.get("ms") or 0.0), 1e-9) / 1e9},
-            "roofline_attention_crossview": None if not agr else {
-                "bound": "hbm", "kernel": "attn_group_lds_kernel (row-wise cross-view attention, ring view mask: one workgroup per (problem, head "
-                                          "group), one wave per query view, K / V of a head copied to LDS once, allowed key views only)",
-                "achieved": timer.group_bytes / (agr["ms"] * 1e-3) / 1e9, "peak": PEAK_HBM_GBPS, "unit": "GB/s",
-                "frac": timer.group_bytes / (agr["ms"] * 1e-3) / 1e9 / PEAK_HBM_GBPS,
-                "algorithmic_bytes_per_launch": timer.group_bytes / agr["launches"], "launches": agr["launches"],
-                "avg_launch_us": agr["avg_us"], "nominal_tflops": agr["tflops"], "share_of_step_time": (agr["ms"] / args.steps) / step_ms},
-            "roofline_attention_pointwise": None if not asm else {
-                "bound": "hbm", "kernel": "attn_small_kernel (point-wise temporal attention, L = frames)",
-                "achieved": timer.small_bytes / (asm["ms"] * 1e-3) / 1e9, "peak": PEAK_HBM_GBPS, "unit": "GB/s",
-                "frac": timer.small_bytes / (asm["ms"] * 1e-3) / 1e9 / PEAK_HBM_GBPS,
-                "algorithmic_bytes_per_launch": timer.small_bytes / asm["launches"], "launches": asm["launches"],
-                "avg_launch_us": asm["avg_us"], "share_of_step_time": (asm["ms"] / args.steps) / step_ms},
-            "whole_step_mfma_frac": step_flop / (step_ms * 1e-3) / (PEAK_BF16_TFLOPS * 1e12),
-            "clock_power": getattr(timer, "clock_power", None),
         }
-        cp = line["clock_power"]
+        if args.full:         # per-kernel figures of the instrumented timed steps + the committed PMC traffic
+            line.update({
+                "roofline": {"bound": "mfma", "kernel": "every dwm_gemm_bf16 launch of the step: gemm4w_kernel (gemm_bf16_4w.hip) where it covers the "
+                                                        "launch, gemm_bf16_kernel otherwise (all epilogues; split in by_kernel)",
+                             "achieved": gm.get("tflops"), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                             "frac": (gm.get("tflops") or 0.0) / PEAK_BF16_TFLOPS, "traffic": gemm_traffic(gm.get("by_kernel")),
+                             "traffic_unit": "L2 -> fabric bytes per launch (TCC_EA request counters: FETCH_SIZE x 2 + WRITE_SIZE in separate rocprofv3 PMC "
+                                             "passes of this command, scripts/pmc_traffic.sh; each kernel's own row, launch-weighted over by_kernel).  "
+                                             "Infinity-Cache (MALL) hits are counted, so this is an UPPER bound of the HBM bytes",
+                             "by_kernel": {k: {kk: vv for kk, vv in v.items() if kk != "ms"} |
+                                           {"share_of_step_time": (v["ms"] / args.steps) / step_ms, "traffic": pmc_traffic(k),
+                                            "traffic_dram_est": pmc_dram(k), "traffic_source": pmc_traffic_file(k)}
+                                           for k, v in (gm.get("by_kernel") or {}).items()},
+                             "algorithmic_flop_per_launch": (gm.get("flops") or 0.0) / max(gm.get("launches") or 1, 1),
+                             "launches": gm.get("launches"), "avg_launch_us": gm.get("avg_us"),
+                             "share_of_step_time": (gm.get("ms", 0.0) / args.steps) / step_ms},
+                "roofline_attention": {"bound": "mfma", "kernel": "attn_stream_kernel (attention_stream.hip: one wave per SIMD, V of a head double-buffered in LDS, K fragments "
+                                                                  "from global memory, Q in AGPRs with the softmax scale folded in by the q RMSNorm; joint L=602, dual L=448, "
+                                                                  "row-wise temporal L=448; round 5: attn_res_kernel)",
+                                       "achieved": at.get("tflops"), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                                       "frac": (at.get("tflops") or 0.0) / PEAK_BF16_TFLOPS,
+                                       "launches": at.get("launches"), "avg_launch_us": at.get("avg_us"),
+                                       "share_of_step_time": (at.get("ms", 0.0) / args.steps) / step_ms,
+                                       "traffic": pmc_traffic("attn_stream_kernel"), "traffic_source": pmc_traffic_file("attn_stream_kernel"),
+                                       "mfma_pipe_busy": pmc_mfma_busy("attn_stream_kernel"),
+                                       "all_attention_launches_tflops": ((at.get("flops") or 0.0) + (asm.get("flops") or 0.0) + (agr.get("flops") or 0.0)) /
+                                       max((at.get("ms") or 0.0) + (asm.get("ms") or 0.0) + (agr.get("ms") or 0.0), 1e-9) / 1e9},
+                "roofline_attention_crossview": None if not agr else {
+                    "bound": "hbm", "kernel": "attn_group_lds_kernel (row-wise cross-view attention, ring view mask: one workgroup per (problem, head "
+                                              "group), one wave per query view, K / V of a head copied to LDS once, allowed key views only)",
+                    "achieved": timer.group_bytes / (agr["ms"] * 1e-3) / 1e9, "peak": PEAK_HBM_GBPS, "unit": "GB/s",
+                    "frac": timer.group_bytes / (agr["ms"] * 1e-3) / 1e9 / PEAK_HBM_GBPS,
+                    "algorithmic_bytes_per_launch": timer.group_bytes / agr["launches"], "launches": agr["launches"],
+                    "avg_launch_us": agr["avg_us"], "nominal_tflops": agr["tflops"], "share_of_step_time": (agr["ms"] / args.steps) / step_ms},
+                "roofline_attention_pointwise": None if not asm else {
+                    "bound": "hbm", "kernel": "attn_small_kernel (point-wise temporal attention, L = frames)",
+                    "achieved": timer.small_bytes / (asm["ms"] * 1e-3) / 1e9, "peak": PEAK_HBM_GBPS, "unit": "GB/s",
+                    "frac": timer.small_bytes / (asm["ms"] * 1e-3) / 1e9 / PEAK_HBM_GBPS,
+                    "algorithmic_bytes_per_launch": timer.small_bytes / asm["launches"], "launches": asm["launches"],
+                    "avg_launch_us": asm["avg_us"], "share_of_step_time": (asm["ms"] / args.steps) / step_ms},
+            })
+        line["whole_step_mfma_frac"] = step_flop / (step_ms * 1e-3) / (PEAK_BF16_TFLOPS * 1e12)
+        if args.full:
+            line["clock_power"] = getattr(timer, "clock_power", None)
+        cp = line.get("clock_power")
         if cp and cp.get("peak_at_sustained_clock_tflops") and gm.get("tflops"):
             # the same launches against what the matrix pipes deliver at the clock the board sustained during this run
             line["roofline"]["frac_of_peak_at_sustained_clock"] = gm["tflops"] / cp["peak_at_sustained_clock_tflops"]
@@ -1226,7 +1271,7 @@ def main():
                 "value": n_samples * args.steps / dt3, "unit": "denoise-steps/s", "ms_per_step": ms3, "flop_per_step": fl["total"],
                 "finite": fin3, "gemm_tflops": t3.summary().get("gemm", {}).get("tflops"),
                 "whole_step_mfma_frac": fl["total"] / (ms3 * 1e-3) / (PEAK_BF16_TFLOPS * 1e12)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(min(os.cpu_count() or 1, int(os.environ.get("DWM_CPU_THREADS", "64"))), args.layout, step_flop)
         print(json.dumps(line))
     D.shutdown()

@@ -177,3 +177,23 @@ def test_bench_kernel_timer_summary_splits_gemm_launches_by_kernel():
     assert s["attn"]["launches"] == 1
     t.four_wave = [True]                      # lengths out of step (a leg that recorded without the counter): no split, no error
     assert "by_kernel" not in t.summary()["gemm"]
+
+
+def test_bench_dump_outputs_writes_float32_npy_on_rank_zero(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): <name>.npy in float32 holding the tensor's values, written by rank 0 only,
+    refused above the size cap; the option is refused outside the headline workload"""
+    import subprocess
+    import numpy as np
+    import bench
+    x = torch.randn(2, 3, 4, dtype=torch.bfloat16)
+    bench.dump_outputs(str(tmp_path / "r1"), {"latents": x}, rank=1)
+    assert not (tmp_path / "r1").exists()
+    bench.dump_outputs(str(tmp_path / "r0"), {"latents": x}, rank=0)
+    a = np.load(tmp_path / "r0" / "latents.npy")
+    assert a.dtype == np.float32 and a.shape == (2, 3, 4) and np.array_equal(a, x.float().numpy())
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": torch.empty(bench.DUMP_LIMIT_BYTES // 4 + 1)})
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--unet", "--dump-outputs", str(tmp_path / "u")],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--dump-outputs" in r.stderr and not (tmp_path / "u").exists()
