@@ -18,10 +18,11 @@
  *   - every function returns 0 on success, a negative DWM_E* code on invalid
  *     arguments (surfaced as RuntimeError by the Python shim) and the positive
  *     hipError_t value if the launch itself failed;
- *   - re-entrant: no global mutable state that a result depends on, and no
- *     environment reads - kernel selection comes from the argument structs only
- *     (what is process-wide: per-kernel "attribute set" flags and the device's CU
- *     count, both idempotent, and two relaxed-atomic launch counters for diagnostics).
+ *   - re-entrant, from any thread and on any device: no global mutable state that a
+ *     result depends on, and no environment reads - kernel selection comes from the
+ *     argument structs only (what is process-wide: idempotent atomic caches per
+ *     (kernel, device) - "dynamic-LDS limit raised" - and per device - its CU count -
+ *     and three relaxed-atomic launch counters for diagnostics).
  */
 #ifndef DWM_HIP_H
 #define DWM_HIP_H
@@ -196,18 +197,21 @@ typedef struct dwm_attn_args {
     int64_t pdiv[3], pmod[3], pstride[3];
     int64_t ldiv[2], lstride[3];
     const uint8_t* mask; int64_t mask_G; int64_t group_size; int64_t p_per_mask;
-    int32_t variant;                           /* 0 = auto.  Kernel selection (attention.hip): bits 0-3 tiled kernel: 2 = 64
-                                                * queries per wave, 1 = 32 (auto: 64 from L = 1024 on); resident kernel: number of
-                                                * compute waves (1-12, the other waves of its 12 only copy), bit 4 online softmax with a
-                                                * running maximum for every unit of the resident kernels (default: their maximum-free
-                                                * fast path with a checked fallback), bit 5 keep the tiled kernel (default for L <= 32:
-                                                * the packed short-sequence kernel; for unmasked self-attention with 64 <= L <= 608:
-                                                * the resident kernel), bit 7 per-wave form of the group-masked kernel, bits 8-11 heads
-                                                * per workgroup / item.  Unmasked self-attention with 225 <= L <= 608 runs the one-wave-per-
-                                                * SIMD streaming form of the resident kernel (attention_stream.hip) by default; bit 13 keeps
-                                                * the 12-wave form (bit 12: the streaming form, as in round 5's opt-in).  Bit 15 is not a
-                                                * kernel choice: q arrives with scale * log2(e) folded in by its producer (`scale` is then
-                                                * ignored; forward kernels) */
+    int32_t variant;                           /* 0 = auto.  Kernel selection (plan_attention in attention.hip), in order of
+                                                * precedence: 1. L <= 32, one segment, no mask, no lse: the packed short-sequence
+                                                * kernel; 2. mask_mode 1, one segment, no lse, G whole groups of 8..32 tokens: the
+                                                * group-masked kernel, its shared (LDS) form for G = 4 / 6 / 8 unless bit 7 (per-wave
+                                                * form); 3. no mask, no lse, not cross, 64 <= L <= 608: the resident kernel - its
+                                                * one-wave-per-SIMD streaming form (attention_stream.hip) for 225 <= L <= 608 unless
+                                                * bit 13 or bits 0-3 are set, else its 12-wave form, bits 0-3 = number of compute
+                                                * waves (1-12, the other waves only copy); 4. everything else: the tiled kernel, bits
+                                                * 0-3: 2 = 64 queries per wave, 1 = 32 (auto: 64 from L = 1024 on).  Bit 5 skips 1-3
+                                                * (keeps the tiled kernel); bit 4 online softmax with a running maximum for every unit
+                                                * of the resident kernels (default: their maximum-free fast path with a checked
+                                                * fallback); bits 8-11 heads per workgroup / item of whichever kernel runs; bit 12 is
+                                                * accepted and ignored (round 5's opt-in to the streaming form).  Bit 15 is not a
+                                                * kernel choice: q arrives with scale * log2(e) folded in by its producer (`scale` is
+                                                * then ignored; forward kernels) */
     int32_t cross;                             /* 1: cross-attention - queries = segment 0 only, keys / values =
                                                 * segment 1 only (q1, k0, v0, o1 unused: pass q1 = q0, k0 = k1, v0 = v1);
                                                 * diffusers BasicTransformerBlock.attn2 (text conditioning of the SD 2.1 UNet) */

@@ -1324,187 +1324,215 @@ tr_probe_kernel(const int* __restrict__ offs, short* __restrict__ out) {
     for (int j = 0; j < 4; ++j) out[lane * 4 + j] = v[j];
 }
 
-template <int QT, int MASK>
-void launch_attn(const AttnParams& P, hipStream_t s) {
-    const int64_t nblk = (int64_t)P.n_problems * (P.heads / P.hpb) * P.nqb;
-    const size_t lds = NSTAGE * STAGE_BYTES + (size_t)((P.L + 3) & ~3) * sizeof(int32_t);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<QT, MASK>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS_BYTES);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((attn_fwd_kernel<QT, MASK>), dim3((unsigned)nblk), dim3(256), lds, s, P);
+// ---- host side: plan (which kernel, which geometry, which parameter block), then launch
+
+enum class AttnKernel { SMALL, GROUP_LDS, GROUP, STREAM, RES, TILED };
+struct AttnPlan {
+    AttnKernel kernel;
+    unsigned grid, block;
+    size_t lds;                 // dynamic LDS bytes
+    int qt, mask;               // TILED: attn_fwd_kernel<qt, mask>
+    int sl;                     // SMALL: attn_small_kernel<sl>
+    int g;                      // GROUP_LDS: attn_group_lds_kernel<g>
+};
+
+// Heads per workgroup: variant bits 8-11 (1..15) when set - the caller checks that they divide `heads` - otherwise the first of the
+// kernel's candidates that divides `heads` and leaves at least min_items (problem, head group) items, 1 if none does.
+int heads_per_wg(const AttnParams& P, int asked, std::initializer_list<int> candidates, int64_t min_items = 0) {
+    if (asked != 0) return asked;
+    for (const int h : candidates)
+        if (P.heads % h == 0 && (int64_t)P.n_problems * (P.heads / h) >= min_items) return h;
+    return 1;
+}
+bool set_heads_per_wg(AttnParams& P, int h) {
+    if (P.heads % h != 0) return false;
+    P.hpb = h;
+    P.fd_heads = make_fastdiv((uint32_t)(P.heads / h));
+    return true;
 }
 
-}  // namespace
-
-// attention_res4.hip
-int dwm_attn_stream_launch(const dwm_attn::AttnParams& P, unsigned nblk, hipStream_t s);
-
-extern "C" int dwm_attention_fwd(const dwm_attn_args* a, void* stream) {
-    AttnParams P;
-    const int rc = fill_params(a, P);
-    if (rc != DWM_OK) return rc;
+// Kernel selection, in order of precedence (host arithmetic only; `ncu` = CUs of the device).  Completes P for the chosen kernel.
+//   0. preconditions of every launch, whichever kernel serves it: the tiled kernel's heads per workgroup must divide `heads`
+//      (DWM_EINVAL), its grid must stay below 2^31 workgroups and its K / V ring + row table must fit the LDS window
+//      (DWM_EUNSUPPORTED).  Every kernel then checks its own heads per workgroup (DWM_EINVAL) and grid (DWM_EUNSUPPORTED).
+//   1. SMALL (attn_small_kernel): L <= 32, one segment, no mask, no LSE - point-wise temporal attention.
+//   2. group-masked (mask_mode 1, one segment, no LSE, G whole groups of 8..32 tokens - row-wise cross-view attention):
+//      GROUP_LDS for G = 4 / 6 / 8 (one workgroup per (problem, head group), K / V of a head copied to LDS once: 6 views are the
+//      camera rigs of every shipped config) unless bit 7; else GROUP (one wave per query group).
+//   3. resident (no mask, no LSE, not cross, 64 <= L <= 608: the K / V rows of one head fit the LDS), persistent, one workgroup
+//      per CU: STREAM (attention_stream.hip) for 8..20 query tiles (225 <= L <= 608) unless bit 13 or bits 0-3 are set or the
+//      launch is one stream_covers() declines; else RES (attn_res_kernel<12>, bits 0-3 = compute waves).
+//   4. TILED (attn_fwd_kernel): everything else; 64 queries per wave on request (bits 0-3 = 2) or by the automatic rule below.
+// Variant bit 5 skips 1-3 (A/B measurements, tests); bit 4 (online softmax for every unit) is read by the resident kernels only;
+// bits 8-11 override the heads per workgroup of whichever kernel runs; bit 12 is accepted and ignored (older callers: "the
+// streaming form"); bit 15 is not a kernel choice (fill_params).
+int plan_attention(AttnParams& P, int variant, bool cross, int ncu, AttnPlan& plan) {
+    const int v_waves = variant & 15;                       // bits 0-3: queries per wave (tiled) / compute waves (resident)
+    const bool v_safe_softmax = ((variant >> 4) & 1) != 0;
+    const bool v_tiled_only = ((variant >> 5) & 1) != 0;
+    const bool v_group_per_wave = ((variant >> 7) & 1) != 0;
+    const int v_heads = (variant >> 8) & 15;
+    const bool v_keep_res = ((variant >> 13) & 1) != 0;
     const int64_t L = P.L;
+    plan = AttnPlan();
+    plan.block = 256;
 
-    // variant bits 0-3, tiled kernel: 2 = 64 queries per wave (256 per workgroup); anything else = 32 (3 workgroups per CU:
-    // measured faster in the full step).  The resident kernel reads the same bits as its number of compute waves.
+    // tiled kernel: 2 = 64 queries per wave (256 per workgroup); anything else = 32 (3 workgroups per CU: measured faster in the
+    // full step).
     // (automatic: 64 queries per wave from L = 1024 on - the UNet's spatial self-attention at L = 1792: 808-843 against 685-715 TFLOP/s;
     //  "full" temporal attention, 19 frames x 448 tokens = 8512 in the shipped UniMLVG example: 628 against 522 TFLOP/s,
     //  profiles/r5y_microbench_attention.log; variant bits 0-3 = 1 keeps 32)
     // (the automatic rule covers what was measured: unmasked inference launches whose 256-query blocks still fill the CUs; masked,
     //  LSE-producing (training) and small-grid launches keep 32 queries per wave unless the caller asks)
     const int64_t blocks64 = (int64_t)P.n_problems * P.heads * ((P.qend + 255) / 256);
-    const bool auto64 = (a->variant & 15) == 0 && L - P.kbeg >= 1024 && P.mask_mode == 0 && P.lse == nullptr && blocks64 >= 512;
-    const int qt = (a->variant & 15) == 2 || auto64 ? 2 : 1;
-    const int qblock = qt * 128;
-    P.nqb = (int)((P.qend + qblock - 1) / qblock);
-    // heads per workgroup: amortises the per-workgroup fixed cost (variant bits 8..11 override: 1..15).
-    // Measured on the step's shapes (L = 168 .. 602): 2 ~ 3 > 1; single-tile problems (L <= 64) take more.
-    P.safe_softmax = (a->variant >> 4) & 1;
-    int hpb = (a->variant >> 8) & 15;
-    if (hpb == 0) {
-        if (L - P.kbeg <= KT) { for (hpb = 6; P.heads % hpb != 0; --hpb) {} }
-        else hpb = P.heads % 2 == 0 ? 2 : P.heads % 3 == 0 ? 3 : 1;
-    }
-    if (P.heads % hpb != 0) return DWM_EINVAL;
-    P.hpb = hpb;
-    P.fd_heads = make_fastdiv((uint32_t)(P.heads / hpb));
+    const bool auto64 = v_waves == 0 && L - P.kbeg >= 1024 && P.mask_mode == 0 && P.lse == nullptr && blocks64 >= 512;
+    const int qt = v_waves == 2 || auto64 ? 2 : 1;
+    P.nqb = (int)((P.qend + qt * 128 - 1) / (qt * 128));
     P.fd_nqb = make_fastdiv((uint32_t)P.nqb);
-    if ((int64_t)P.n_problems * (P.heads / P.hpb) * P.nqb >= (1ll << 31)) return DWM_EUNSUPPORTED;
-    if (NSTAGE * STAGE_BYTES + L * 4 + 16 > MAX_LDS_BYTES) return DWM_EUNSUPPORTED;   // ring + row table must fit the LDS window
-    hipStream_t s = (hipStream_t)stream;
-    // short single-segment sequences without a mask (point-wise temporal attention): the packed small-L kernel;
-    // variant bit 5 keeps the tiled kernel (A/B measurements, tests)
-    if (L <= 32 && P.L1 == 0 && P.mask_mode == 0 && P.lse == nullptr && !((a->variant >> 5) & 1)) {
-        int hs = (a->variant >> 8) & 15;
-        if (hs == 0) { for (hs = 8; P.heads % hs != 0; --hs) {} }
-        if (P.heads % hs != 0) return DWM_EINVAL;
-        P.hpb = hs;
-        P.fd_heads = make_fastdiv((uint32_t)(P.heads / hs));
-        const int sl = L <= 8 ? 8 : L <= 16 ? 16 : 32;
-        const int64_t ngrp = ((int64_t)P.n_problems + 32 / sl - 1) / (32 / sl);
-        const int64_t nblk = ((ngrp + 3) / 4) * (P.heads / hs);
+    P.safe_softmax = v_safe_softmax;
+    // heads per workgroup amortise the per-workgroup fixed cost.  Measured on the step's shapes (L = 168 .. 602): 2 ~ 3 > 1;
+    // single-tile problems (L <= 64) take more.
+    if (!set_heads_per_wg(P, L - P.kbeg <= KT ? heads_per_wg(P, v_heads, {6, 5, 4, 3, 2}) : heads_per_wg(P, v_heads, {2, 3}))) return DWM_EINVAL;
+    const int64_t tiled_grid = (int64_t)P.n_problems * (P.heads / P.hpb) * P.nqb;
+    if (tiled_grid >= (1ll << 31)) return DWM_EUNSUPPORTED;
+    if (NSTAGE * STAGE_BYTES + L * 4 + 16 > MAX_LDS_BYTES) return DWM_EUNSUPPORTED;
+
+    if (!v_tiled_only && L <= 32 && P.L1 == 0 && P.mask_mode == 0 && P.lse == nullptr) {
+        if (!set_heads_per_wg(P, heads_per_wg(P, v_heads, {8, 7, 6, 5, 4, 3, 2}))) return DWM_EINVAL;
+        plan.kernel = AttnKernel::SMALL;
+        plan.sl = L <= 8 ? 8 : L <= 16 ? 16 : 32;
+        const int64_t ngrp = ((int64_t)P.n_problems + 32 / plan.sl - 1) / (32 / plan.sl);
+        const int64_t nblk = ((ngrp + 3) / 4) * (P.heads / P.hpb);
         if (nblk >= (1ll << 31)) return DWM_EUNSUPPORTED;
-        if (sl == 8) hipLaunchKernelGGL((attn_small_kernel<8>), dim3((unsigned)nblk), dim3(256), 0, s, P);
-        else if (sl == 16) hipLaunchKernelGGL((attn_small_kernel<16>), dim3((unsigned)nblk), dim3(256), 0, s, P);
-        else hipLaunchKernelGGL((attn_small_kernel<32>), dim3((unsigned)nblk), dim3(256), 0, s, P);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? DWM_OK : (int)e;
+        plan.grid = (unsigned)nblk;
+        return DWM_OK;
     }
-    // group-masked problems made of G whole groups of <= 32 tokens (row-wise cross-view attention): one wave per query group,
-    // only the key groups its mask row allows; variant bit 5 keeps the tiled kernel (A/B measurements, tests)
-    if (P.mask_mode == 1 && P.L1 == 0 && P.lse == nullptr && P.group_size >= 8 && P.group_size <= 32 && (int64_t)P.mask_G * P.group_size == L &&
-        !((a->variant >> 5) & 1)) {
-        // shared form (one workgroup per (problem, head group), K / V of a head copied to LDS once): G = 6 views (the camera
-        // rigs of every shipped config) or 4 / 8; variant bit 7 keeps the per-wave form (A/B measurements, tests)
-        if ((P.mask_G == 6 || P.mask_G == 4 || P.mask_G == 8) && !((a->variant >> 7) & 1)) {
-            int hs = (a->variant >> 8) & 15;
-            if (hs == 0) { for (hs = 8; P.heads % hs != 0; --hs) {} }      // heads per workgroup (the double-buffered copy pipeline runs over them)
-            if (P.heads % hs != 0) return DWM_EINVAL;
-            P.hpb = hs;
-            P.fd_heads = make_fastdiv((uint32_t)(P.heads / hs));
-            const int64_t nblk = (int64_t)P.n_problems * (P.heads / hs);
+    if (!v_tiled_only && P.mask_mode == 1 && P.L1 == 0 && P.lse == nullptr && P.group_size >= 8 && P.group_size <= 32 &&
+        (int64_t)P.mask_G * P.group_size == L) {
+        // (GROUP_LDS: the double-buffered copy pipeline runs over the heads of a workgroup)
+        if (!set_heads_per_wg(P, heads_per_wg(P, v_heads, {8, 7, 6, 5, 4, 3, 2}))) return DWM_EINVAL;
+        const int G = P.mask_G;
+        if ((G == 6 || G == 4 || G == 8) && !v_group_per_wave) {
+            plan.kernel = AttnKernel::GROUP_LDS;
+            plan.g = G;
+            const int64_t nblk = (int64_t)P.n_problems * (P.heads / P.hpb);
             if (nblk >= (1ll << 31)) return DWM_EUNSUPPORTED;
-            const int G = P.mask_G;
-            const size_t lds = (size_t)4 * G * GRP_IMG + (size_t)G * 4096;        // two stages of K + V images, output regions
-#define DWM_GRP(G_)                                                                                              \
-            do {                                                                                                 \
-                static bool attr_set = false;                                                                    \
-                if (!attr_set) {                                                                                 \
-                    (void)hipFuncSetAttribute((const void*)attn_group_lds_kernel<G_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                    attr_set = true;                                                                             \
-                }                                                                                                \
-                hipLaunchKernelGGL((attn_group_lds_kernel<G_>), dim3((unsigned)nblk), dim3(G_ * 64), lds, s, P); \
-            } while (0)
-            if (G == 6) DWM_GRP(6); else if (G == 4) DWM_GRP(4); else DWM_GRP(8);
-#undef DWM_GRP
-            const hipError_t e = hipGetLastError();
-            return e == hipSuccess ? DWM_OK : (int)e;
+            plan.grid = (unsigned)nblk;
+            plan.block = (unsigned)G * 64;
+            plan.lds = (size_t)4 * G * GRP_IMG + (size_t)G * 4096;        // two stages of K + V images, output regions
+            return DWM_OK;
         }
-        int hs = (a->variant >> 8) & 15;
-        if (hs == 0) { for (hs = 8; P.heads % hs != 0; --hs) {} }
-        if (P.heads % hs != 0) return DWM_EINVAL;
-        P.hpb = hs;
-        P.fd_heads = make_fastdiv((uint32_t)(P.heads / hs));
-        const int64_t units = (int64_t)P.n_problems * P.mask_G;
-        const int64_t nblk = ((units + 3) / 4) * (P.heads / hs);
+        plan.kernel = AttnKernel::GROUP;
+        const int64_t units = (int64_t)P.n_problems * G;
+        const int64_t nblk = ((units + 3) / 4) * (P.heads / P.hpb);
         if (nblk >= (1ll << 31) || units >= (1ll << 31)) return DWM_EUNSUPPORTED;
-        hipLaunchKernelGGL(attn_group_kernel, dim3((unsigned)nblk), dim3(256), 0, s, P);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? DWM_OK : (int)e;
+        plan.grid = (unsigned)nblk;
+        return DWM_OK;
     }
-    // resident form: no mask, no LSE, self-attention, the K / V rows of one head fit the LDS (L <= 608); variant bit 5 keeps
-    // the tiled kernel (A/B measurements, tests)
 #ifdef DWM_ATTN_TRACE
     const bool res_lse_ok = true;              // the lse buffer is the trace buffer in this build
 #else
     const bool res_lse_ok = P.lse == nullptr;
 #endif
-    if (P.mask_mode == 0 && res_lse_ok && !a->cross && L <= 608 && L >= 64 && !((a->variant >> 5) & 1)) {
-        int hs = (a->variant >> 8) & 15;
-        if (hs == 0) {                             // heads per item: as many as leave >= 3 items per CU
-            for (hs = 6; hs > 1; --hs)
-                if (P.heads % hs == 0 && (int64_t)P.n_problems * (P.heads / hs) >= 768) break;
-        }
-        if (P.heads % hs != 0) return DWM_EINVAL;
-        P.hpb = hs;
-        P.fd_heads = make_fastdiv((uint32_t)(P.heads / hs));
-        const int64_t nitems = (int64_t)P.n_problems * (P.heads / hs);
+    if (!v_tiled_only && P.mask_mode == 0 && res_lse_ok && !cross && L <= 608 && L >= 64) {
+        // heads per item: as many as leave >= 3 items per CU
+        if (!set_heads_per_wg(P, heads_per_wg(P, v_heads, {6, 5, 4, 3, 2}, 768))) return DWM_EINVAL;
+        const int64_t nitems = (int64_t)P.n_problems * (P.heads / P.hpb);
         if (nitems >= (1ll << 31)) return DWM_EUNSUPPORTED;
-        static int ncu = 0;
-        if (ncu == 0) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return DWM_EINVAL;
-            ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+        plan.grid = (unsigned)(nitems < ncu ? nitems : ncu);               // persistent: one workgroup per CU
+        P.nwc = v_waves == 0 ? 12 : v_waves;                               // compute waves (12 = all)
+        if (P.nwc > 12) return DWM_EINVAL;
+        // the one-wave-per-SIMD streaming form (4 waves, all query tiles of a wave in one pass over the keys, V double-buffered in
+        // LDS, K fragments from global memory, Q in AGPRs): 778-808 against 740-755 TFLOP/s at L = 602, 655-690 against 590-610 at
+        // L = 448 (profiles/r6g2_*)
+        const int nqt = (P.qend + 31) >> 5;
+        if (!v_keep_res && v_waves == 0 && nqt >= 8 && nqt <= 20 && stream_covers(P)) {
+            plan.kernel = AttnKernel::STREAM;
+            plan.lds = stream_lds_bytes(P.L);                              // (what its launcher asks for)
+            P.stream_far = stream_far(P);
+            return DWM_OK;
         }
-        const unsigned nblk = (unsigned)(nitems < ncu ? nitems : ncu);           // persistent: one workgroup per CU
-        const size_t lds = (size_t)2 * ((L + 31) & ~31) * 128 + (size_t)3 * ((L + 3) & ~3) * sizeof(int32_t);
-        // compute waves (variant bits 0-3 override; 12 = all)
-        {
-            int nwc = a->variant & 15;
-            if (nwc == 0) nwc = 12;
-            if (nwc < 1 || nwc > 12) return DWM_EINVAL;
-            P.nwc = nwc;
-        }
-        // one-wave-per-SIMD streaming form (attention_stream.hip: 4 waves, all query tiles of a wave in one pass over the keys, V
-        // double-buffered in LDS, K fragments from global memory, Q in AGPRs): the DEFAULT for 8..20 query tiles (225 <= L <= 608) -
-        // 778-808 against 740-755 TFLOP/s at L = 602, 655-690 against 590-610 at L = 448 (profiles/r6g2_*).  Variant bit 13 keeps
-        // attn_res_kernel (A/B measurements, tests), as does an explicit wave count (bits 0-3); bit 12 is accepted as "the
-        // streaming form" for older callers.
-        {
-            const int nqt = (P.qend + 31) >> 5;
-            const bool keep12 = ((a->variant >> 13) & 1) != 0;
-            if (!keep12 && nqt >= 8 && nqt <= 20 && (a->variant & 15) == 0) {
-                const int rc4 = dwm_attn_stream_launch(P, nblk, s);
-                if (rc4 >= 0) return rc4;                 // (-1: a launch it does not cover after all - segment displacements, LDS)
-            }
-        }
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)attn_res_kernel<12>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr_set = true;
-        }
-        hipLaunchKernelGGL((attn_res_kernel<12>), dim3(nblk), dim3(768), lds, s, P);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? DWM_OK : (int)e;
+        plan.kernel = AttnKernel::RES;
+        plan.block = 768;
+        plan.lds = (size_t)2 * ((L + 31) & ~31) * 128 + (size_t)3 * ((L + 3) & ~3) * sizeof(int32_t);
+        return DWM_OK;
     }
-#define DWM_ATTN(QT_)                                              \
-    do {                                                           \
-        if (P.mask_mode == 0) launch_attn<QT_, 0>(P, s);           \
-        else if (P.mask_mode == 1) launch_attn<QT_, 1>(P, s);      \
-        else launch_attn<QT_, 2>(P, s);                            \
-    } while (0)
-    if (qt == 1) DWM_ATTN(1); else DWM_ATTN(2);
-#undef DWM_ATTN
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DWM_OK : (int)e;
+    plan.kernel = AttnKernel::TILED;
+    plan.qt = qt;
+    plan.mask = P.mask_mode;
+    plan.grid = (unsigned)tiled_grid;
+    plan.lds = NSTAGE * STAGE_BYTES + (size_t)((P.L + 3) & ~3) * sizeof(int32_t);
+    return DWM_OK;
+}
+
+int launch_small(const AttnParams& P, const AttnPlan& pl, hipStream_t s) {
+    const dim3 grid(pl.grid), block(pl.block);
+    if (pl.sl == 8) hipLaunchKernelGGL((attn_small_kernel<8>), grid, block, 0, s, P);
+    else if (pl.sl == 16) hipLaunchKernelGGL((attn_small_kernel<16>), grid, block, 0, s, P);
+    else hipLaunchKernelGGL((attn_small_kernel<32>), grid, block, 0, s, P);
+    return dwm_launch_status();
+}
+
+template <int G>
+int launch_group_lds_g(const AttnParams& P, const AttnPlan& pl, hipStream_t s) {
+    const hipError_t e = dwm_allow_dynamic_lds<attn_group_lds_kernel<G>>(160 * 1024);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL((attn_group_lds_kernel<G>), dim3(pl.grid), dim3(pl.block), pl.lds, s, P);
+    return dwm_launch_status();
+}
+int launch_group_lds(const AttnParams& P, const AttnPlan& pl, hipStream_t s) {
+    return pl.g == 6 ? launch_group_lds_g<6>(P, pl, s) : pl.g == 4 ? launch_group_lds_g<4>(P, pl, s) : launch_group_lds_g<8>(P, pl, s);
+}
+
+int launch_group(const AttnParams& P, const AttnPlan& pl, hipStream_t s) {
+    hipLaunchKernelGGL(attn_group_kernel, dim3(pl.grid), dim3(pl.block), 0, s, P);
+    return dwm_launch_status();
+}
+
+int launch_res(const AttnParams& P, const AttnPlan& pl, hipStream_t s) {
+    const hipError_t e = dwm_allow_dynamic_lds<attn_res_kernel<12>>(160 * 1024);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL((attn_res_kernel<12>), dim3(pl.grid), dim3(pl.block), pl.lds, s, P);
+    return dwm_launch_status();
+}
+
+template <int QT, int MASK>
+int launch_tiled_qm(const AttnParams& P, const AttnPlan& pl, hipStream_t s) {
+    const hipError_t e = dwm_allow_dynamic_lds<attn_fwd_kernel<QT, MASK>>(MAX_LDS_BYTES);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL((attn_fwd_kernel<QT, MASK>), dim3(pl.grid), dim3(pl.block), pl.lds, s, P);
+    return dwm_launch_status();
+}
+int launch_tiled(const AttnParams& P, const AttnPlan& pl, hipStream_t s) {
+    if (pl.qt == 1) return pl.mask == 0 ? launch_tiled_qm<1, 0>(P, pl, s) : pl.mask == 1 ? launch_tiled_qm<1, 1>(P, pl, s) : launch_tiled_qm<1, 2>(P, pl, s);
+    return pl.mask == 0 ? launch_tiled_qm<2, 0>(P, pl, s) : pl.mask == 1 ? launch_tiled_qm<2, 1>(P, pl, s) : launch_tiled_qm<2, 2>(P, pl, s);
+}
+
+}  // namespace
+
+// attention_stream.hip: the STREAM launch (attn_stream_kernel lives in that translation unit)
+int dwm_attn_stream_launch(const dwm_attn::AttnParams& P, unsigned nblk, hipStream_t s);
+
+extern "C" int dwm_attention_fwd(const dwm_attn_args* a, void* stream) {
+    AttnParams P;
+    int rc = fill_params(a, P);
+    if (rc != DWM_OK) return rc;
+    AttnPlan plan;
+    rc = plan_attention(P, a->variant, a->cross != 0, dwm_cu_count(), plan);
+    if (rc != DWM_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    switch (plan.kernel) {
+        case AttnKernel::SMALL: return launch_small(P, plan, s);
+        case AttnKernel::GROUP_LDS: return launch_group_lds(P, plan, s);
+        case AttnKernel::GROUP: return launch_group(P, plan, s);
+        case AttnKernel::STREAM: return dwm_attn_stream_launch(P, plan.grid, s);
+        case AttnKernel::RES: return launch_res(P, plan, s);
+        default: return launch_tiled(P, plan, s);
+    }
 }
 
 extern "C" int dwm_debug_tr_probe(const int32_t* offs, int16_t* out, void* stream) {
     if (offs == nullptr || out == nullptr) return DWM_EINVAL;
     hipLaunchKernelGGL(tr_probe_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const int*)offs, (short*)out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DWM_OK : (int)e;
+    return dwm_launch_status();
 }

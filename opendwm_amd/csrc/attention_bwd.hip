@@ -486,18 +486,14 @@ int launch_bwd(const AttnParams& P, hipStream_t s) {
     const int64_t nblk = (int64_t)P.n_problems * P.heads * P.nqb, nblk_k = (int64_t)P.n_problems * P.heads * Pk.nqb;
     const size_t tab = (size_t)((P.L + 3) & ~3) * sizeof(int32_t);
     const size_t lds_q = 2 * DQ_STAGE + tab, lds_kv = 2 * DKV_STAGE + tab;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)attn_dq_kernel<MASK>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        (void)hipFuncSetAttribute((const void*)attn_dkv_kernel<MASK>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        attr_set = true;
-    }
+    hipError_t e = dwm_allow_dynamic_lds<attn_dq_kernel<MASK>>(128 * 1024);
+    if (e == hipSuccess) e = dwm_allow_dynamic_lds<attn_dkv_kernel<MASK>>(128 * 1024);
+    if (e != hipSuccess) return (int)e;
     if (lds_kv > 128 * 1024) return DWM_EUNSUPPORTED;
     hipLaunchKernelGGL(delta_kernel, dim3((unsigned)(((int64_t)P.n_problems * P.L + 3) / 4)), dim3(256), 0, s, P);
     hipLaunchKernelGGL((attn_dq_kernel<MASK>), dim3((unsigned)nblk), dim3(256), lds_q, s, P);
     hipLaunchKernelGGL((attn_dkv_kernel<MASK>), dim3((unsigned)nblk_k), dim3(256), lds_kv, s, Pk);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DWM_OK : (int)e;
+    return dwm_launch_status();
 }
 
 }  // namespace

@@ -36,7 +36,7 @@ struct AttnParams {
     bf16_t *dq0, *dk0, *dv0;             // gradients, addressed like q0 / k0 / v0 with ld_d0 / ld_d1
     int64_t ld_d0, ld_d1, dseg1_delta;   // (dq1 - dq0) == (dk1 - dk0) == (dv1 - dv0)
     int64_t oseg1_delta, doseg1_delta;   // o1 - o0, do1 - do0 in elements
-    int stream_far;          // attn_stream_kernel only (set by its launcher): the segment displacements are added per row, not folded into the tables
+    int stream_far;          // attn_stream_kernel only (stream_far() below): the segment displacements are added per row, not folded into the tables
     float* delta;                        // [n_problems, heads, L] -rowsum(dO * O)
     float scale;
     int n_problems, heads, nqb;
@@ -97,7 +97,7 @@ DWM_DEVINL bf16x8 scale_frag(const bf16x8& v, float c) {
 }
 
 
-// ---- pieces shared by the resident forward kernels (attention.hip: attn_res_kernel; attention_res4.hip: attn_res4_kernel)
+// ---- pieces shared by the resident forward kernels (attention.hip: attn_res_kernel; attention_stream.hip: attn_stream_kernel)
 // One 32-key step by the textbook online softmax (running max m and sum l per lane, rescale every step): the fallback of a
 // unit whose fast-path sums left the safe range.  It reads K and V from GLOBAL memory, not from the images: by the time a unit
 // knows that it needs the fallback, the first sub-tiles of the images may already hold the NEXT head's rows (the refill point
@@ -229,6 +229,25 @@ inline int fill_params(const dwm_attn_args* a, AttnParams& P) {
     P.fd_G = make_fastdiv((uint32_t)(P.mask_G > 0 ? P.mask_G : 1));
     P.fd_ppm = make_fastdiv((uint32_t)(P.p_per_mask > 0 ? P.p_per_mask : 1));
     return DWM_OK;
+}
+
+// ---- host side: what attn_stream_kernel (attention_stream.hip) covers among the launches of the resident form, for the plan of
+// dwm_attention_fwd.  Its row tables hold offsets from q0 / k0 / v0 / o0 in 16-byte units as int32: both segment displacements
+// must be whole units, and the V images of a head plus the tables must fit the LDS.
+inline size_t stream_lds_bytes(int L) {
+    const int Lp = (L + 31) & ~31;
+    return (size_t)2 * Lp * 128 + (size_t)3 * Lp * sizeof(int32_t);
+}
+inline bool stream_covers(const AttnParams& P) {
+    return P.seg1_delta % 8 == 0 && P.oseg1_delta % 8 == 0 && stream_lds_bytes(P.L) <= 160 * 1024;
+}
+// Within +-16 GiB a displacement is folded into the segment-1 entries (no select on the way from an entry to an address); two
+// segments in SEPARATE allocations may lie further apart - a caching allocator on a 288-GB device hands out such pairs - and run
+// the FAR instantiation: entries relative to each segment, the displacement added per row.  Same arithmetic on the same values
+// either way: the results are bit-identical (tests/test_round6_gpu.py places the segments 20 GiB apart).
+inline int stream_far(const AttnParams& P) {
+    const int64_t lim = 1ll << 33;
+    return (P.seg1_delta <= -lim || P.seg1_delta >= lim || P.oseg1_delta <= -lim || P.oseg1_delta >= lim) ? 1 : 0;
 }
 
 }  // namespace dwm_attn

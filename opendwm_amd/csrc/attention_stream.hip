@@ -691,35 +691,19 @@ attn_stream_kernel(const AttnParams P) {
 
 }  // namespace
 
-// Called by dwm_attention_fwd (attention.hip) for the launches this kernel covers: unmasked self-attention whose V rows of a head
-// fit the LDS twice, 8 <= query tiles <= 20 (225 <= L <= 608: two to five tiles per wave).
+// Called by dwm_attention_fwd (attention.hip) for the launches its plan gives to this kernel: unmasked self-attention whose V rows
+// of a head fit the LDS twice, 8 <= query tiles <= 20 (225 <= L <= 608: two to five tiles per wave), stream_covers()
+// (attention_common.h); P.stream_far is set by the plan.
 static std::atomic<int64_t> g_stream_launches{0};           // launches served (dwm_attn_stream_launches: diagnostics, relaxed)
 extern "C" int64_t dwm_attn_stream_launches(void) { return g_stream_launches.load(std::memory_order_relaxed); }
 
 int dwm_attn_stream_launch(const dwm_attn::AttnParams& P, unsigned nblk, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)attn_stream_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
-    // the row tables hold offsets from q0 / k0 / v0 / o0 in 16-byte units as int32: both segment displacements must be whole units
-    // (otherwise: -1, the caller keeps attn_res_kernel).  Within +-16 GiB the displacement is folded into the segment-1 entries (no
-    // select on the way from an entry to an address); two segments in SEPARATE allocations may lie further apart - a caching
-    // allocator on a 288-GB device hands out such pairs - and run the FAR instantiation: entries relative to each segment, the
-    // displacement added per row.  Same arithmetic on the same values either way: the results are bit-identical
-    // (tests/test_round6_gpu.py places the segments 20 GiB apart).
-    if (P.seg1_delta % 8 != 0 || P.oseg1_delta % 8 != 0) return -1;
-    const int64_t lim = 1ll << 33;
-    dwm_attn::AttnParams Pk = P;
-    Pk.stream_far = (P.seg1_delta <= -lim || P.seg1_delta >= lim || P.oseg1_delta <= -lim || P.oseg1_delta >= lim) ? 1 : 0;
-    const int Lp = (P.L + 31) & ~31;
-    const size_t lds = (size_t)2 * Lp * 128 + (size_t)3 * Lp * sizeof(int32_t);
-    if (lds > 160 * 1024) return -1;
+    const hipError_t e = dwm_allow_dynamic_lds<attn_stream_kernel>(160 * 1024);
+    if (e != hipSuccess) return (int)e;
 #ifdef ST_X_NBLK
     if (nblk > ST_X_NBLK) nblk = ST_X_NBLK;                 // (experiment builds: fewer workgroups - is the seam's store time a per-CU or a chip-wide limit?)
 #endif
-    hipLaunchKernelGGL(attn_stream_kernel, dim3(nblk), dim3(256), lds, s, Pk);
+    hipLaunchKernelGGL(attn_stream_kernel, dim3(nblk), dim3(256), dwm_attn::stream_lds_bytes(P.L), s, P);
     g_stream_launches.fetch_add(1, std::memory_order_relaxed);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DWM_OK : (int)e;
+    return dwm_launch_status();
 }

@@ -1,8 +1,11 @@
-// Shared device helpers for the gfx950 (CDNA4, wave64) kernels of libdwm_hip.so.
+// Shared device helpers and host-side launch helpers for the gfx950 (CDNA4, wave64) kernels of libdwm_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
+#include <initializer_list>
 #include <type_traits>
+#include "dwm_hip.h"
 
 typedef uint16_t bf16_t;                                         // raw bfloat16 storage
 typedef __attribute__((ext_vector_type(8))) short bf16x8;        // MFMA A/B operand (8 bf16, 4 VGPR)
@@ -173,3 +176,36 @@ DWM_DEVINL uint32_t fdiv(uint32_t n, const FastDiv& f) { return (__umulhi(f.m, n
 DWM_DEVINL uint32_t fmod_u(uint32_t n, const FastDiv& f) { return n - fdiv(n, f) * f.d; }
 
 static inline bool dwm_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+
+// ---- host-side launch helpers.  Their caches are per device and idempotent (a lost race repeats a harmless call), so any thread
+// may launch on any device; the steady-state cost is one hipGetDevice and one atomic load.
+// Raises the dynamic-LDS limit of Kernel to `bytes`, once per (kernel, current device; devices >= 64: every time).  Keyed on the
+// kernel itself, not on its type: the instantiations of a kernel template share one function-pointer type.
+template <auto Kernel>
+inline hipError_t dwm_allow_dynamic_lds(int bytes) {
+    static std::atomic<uint64_t> done{0};
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const uint64_t bit = dev < 64 ? 1ull << dev : 0;
+    if (done.load(std::memory_order_acquire) & bit) return hipSuccess;
+    e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) done.fetch_or(bit, std::memory_order_release);
+    return e;
+}
+// CU count of the current device (256 if the runtime does not say), cached for devices < 64
+inline int dwm_cu_count() {
+    static std::atomic<int> cached[64];                // 0: not asked yet
+    int dev = 0, ncu = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    std::atomic<int>* const slot = dev < 64 ? &cached[dev] : nullptr;
+    if (slot != nullptr && (ncu = slot->load(std::memory_order_relaxed)) > 0) return ncu;
+    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
+    if (slot != nullptr) slot->store(ncu, std::memory_order_relaxed);
+    return ncu;
+}
+// status of the launches just enqueued: DWM_OK or the positive hipError_t
+inline int dwm_launch_status() {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? DWM_OK : (int)e;
+}

@@ -339,10 +339,6 @@ add_f32_f32_inplace_kernel(float* __restrict__ y, const float* __restrict__ x, i
     *(float4*)(y + i * 4) = a;
 }
 
-inline int finish() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DWM_OK : (int)e;
-}
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
@@ -358,7 +354,7 @@ extern "C" int dwm_silu(const void* x, void* y, int64_t n, void* stream) {
     if (n % 8 != 0 || !dwm_aligned16(x) || !dwm_aligned16(y)) return DWM_EALIGN;
     hipLaunchKernelGGL(silu_kernel, dim3(blocks_for(n / 8)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)x, (bf16_t*)y, n / 8);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_timestep_sinusoid(const float* t, int64_t n, int32_t C, void* out, void* stream) {
@@ -366,7 +362,7 @@ extern "C" int dwm_timestep_sinusoid(const float* t, int64_t n, int32_t C, void*
     if (C % 2 != 0) return DWM_EUNSUPPORTED;
     hipLaunchKernelGGL(sinusoid_kernel, dim3(blocks_for(n * (C / 2))), dim3(256), 0, (hipStream_t)stream,
                        t, n, C, (bf16_t*)out);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_patchify(const void* x, int32_t x_is_f32, int64_t I, int32_t C, int32_t H, int32_t W,
@@ -380,7 +376,7 @@ extern "C" int dwm_patchify(const void* x, int32_t x_is_f32, int64_t I, int32_t 
     else
         hipLaunchKernelGGL(patchify_kernel<bf16_t>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream,
                            (const bf16_t*)x, I, C, H, W, p, (bf16_t*)out, ldo);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_unpatchify(const void* x, int64_t ldx, int64_t I, int32_t C, int32_t h, int32_t w,
@@ -390,7 +386,7 @@ extern "C" int dwm_unpatchify(const void* x, int64_t ldx, int64_t I, int32_t C, 
     const int64_t total = I * C * h * p * w * p;
     hipLaunchKernelGGL(unpatchify_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)x, ldx, I, C, h, w, p, (bf16_t*)out);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_cfg_euler_step(const void* pred, float* latents, void* model_in, int64_t n,
@@ -400,7 +396,7 @@ extern "C" int dwm_cfg_euler_step(const void* pred, float* latents, void* model_
         return DWM_EALIGN;
     hipLaunchKernelGGL(cfg_euler_kernel, dim3(blocks_for(n / 4)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)pred, latents, (bf16_t*)model_in, n, guidance, dsigma, (const float*)nullptr, (int64_t)1);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_cfg_euler_step_grouped(const void* pred, float* latents, void* model_in, int64_t n, float guidance,
@@ -411,7 +407,7 @@ extern "C" int dwm_cfg_euler_step_grouped(const void* pred, float* latents, void
         return DWM_EALIGN;
     hipLaunchKernelGGL(cfg_euler_kernel, dim3(blocks_for(n / 4)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)pred, latents, (bf16_t*)model_in, n, guidance, 0.f, dsigma, group_elems);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_cfg_multistep(const void* pred, float* latents, float* x0_prev, void* model_in, int64_t n, float guidance,
@@ -422,7 +418,7 @@ extern "C" int dwm_cfg_multistep(const void* pred, float* latents, float* x0_pre
         return DWM_EALIGN;
     hipLaunchKernelGGL(cfg_multistep_kernel<bf16_t>, dim3(blocks_for(n / 4)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)pred,
                        latents, x0_prev, (bf16_t*)model_in, n, guidance, kx, ko, A, B, C);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_cfg_multistep_f32(const float* pred, float* latents, float* x0_prev, float* model_in, int64_t n, float guidance,
@@ -432,7 +428,7 @@ extern "C" int dwm_cfg_multistep_f32(const float* pred, float* latents, float* x
         return DWM_EALIGN;
     hipLaunchKernelGGL(cfg_multistep_kernel<float>, dim3(blocks_for(n / 4)), dim3(256), 0, (hipStream_t)stream, pred,
                        latents, x0_prev, model_in, n, guidance, kx, ko, A, B, C);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_frame_affine(const float* x, const float* y, const float* coef, float* out, void* out_bf16, int64_t n,
@@ -443,7 +439,7 @@ extern "C" int dwm_frame_affine(const float* x, const float* y, const float* coe
         return DWM_EALIGN;
     hipLaunchKernelGGL(frame_affine_kernel, dim3(blocks_for(n / 4)), dim3(256), 0, (hipStream_t)stream, x, y, coef, out,
                        (bf16_t*)out_bf16, n, group_elems);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_cfg_ddim_step(const void* pred, int32_t pred_is_f32, int32_t cfg, float* latents, void* model_in, float* x0_out,
@@ -464,20 +460,20 @@ extern "C" int dwm_cfg_ddim_step(const void* pred, int32_t pred_is_f32, int32_t 
         hipLaunchKernelGGL(cfg_ddim_kernel<bf16_t>, dim3(blocks_for(n / 4)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)pred, off,
                            latents, (bf16_t*)model_in, x0_out, noise, coef, n, group_elems, guidance, prediction_type, clip_range,
                            use_clipped_model_output);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_ray_features(const float* cam, int64_t I, int32_t h, int32_t w, void* out, int64_t ldo, void* stream) {
     if (cam == nullptr || out == nullptr || I <= 0 || h <= 0 || w <= 0 || ldo < 72) return DWM_EINVAL;
     hipLaunchKernelGGL(ray_features_kernel<bf16_t>, dim3(blocks_for(I * h * w)), dim3(256), 0, (hipStream_t)stream, cam, I, h, w,
                        (bf16_t*)out, ldo);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_ray_features_f32(const float* cam, int64_t I, int32_t h, int32_t w, float* out, int64_t ldo, void* stream) {
     if (cam == nullptr || out == nullptr || I <= 0 || h <= 0 || w <= 0 || ldo < 72) return DWM_EINVAL;
     hipLaunchKernelGGL(ray_features_kernel<float>, dim3(blocks_for(I * h * w)), dim3(256), 0, (hipStream_t)stream, cam, I, h, w, out, ldo);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream) {
@@ -485,7 +481,7 @@ extern "C" int dwm_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void
     if (n % 4 != 0 || !dwm_aligned16(src) || (((uintptr_t)dst) & 7u)) return DWM_EALIGN;
     hipLaunchKernelGGL(cast_kernel, dim3(blocks_for(n / 4)), dim3(256), 0, (hipStream_t)stream, src,
                        (bf16_t*)dst, n);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_unshuffle_tokens(const void* x, int32_t x_is_f32, int64_t I, int32_t C, int32_t H, int32_t W,
@@ -499,7 +495,7 @@ extern "C" int dwm_unshuffle_tokens(const void* x, int32_t x_is_f32, int64_t I, 
     else
         hipLaunchKernelGGL(unshuffle_tokens_kernel<bf16_t>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream,
                            (const bf16_t*)x, I, C, H, W, r, (bf16_t*)out, ldo);
-    return finish();
+    return dwm_launch_status();
 }
 
 static int avgpool2_impl(const void* x, int64_t I, int32_t h, int32_t w, int32_t C, void* out, void* stream, bool f32) {
@@ -511,7 +507,7 @@ static int avgpool2_impl(const void* x, int64_t I, int32_t h, int32_t w, int32_t
                                 (const float*)x, I, h, w, C / 8, (float*)out);
     else hipLaunchKernelGGL(avgpool2_tokens_kernel<bf16_t>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream,
                             (const bf16_t*)x, I, h, w, C / 8, (bf16_t*)out);
-    return finish();
+    return dwm_launch_status();
 }
 extern "C" int dwm_avgpool2_tokens(const void* x, int64_t I, int32_t h, int32_t w, int32_t C, void* out, void* stream) {
     return avgpool2_impl(x, I, h, w, C, out, stream, false);
@@ -528,7 +524,7 @@ extern "C" int dwm_unshuffle_tokens_f32(const float* x, int64_t I, int32_t C, in
     const int64_t total = I * (H / r) * (W / r) * ldo;
     hipLaunchKernelGGL((unshuffle_tokens_kernel<float, float>), dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream,
                        x, I, C, H, W, r, out, ldo);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_add_f32_inplace(void* y, const float* x, int64_t n, void* stream) {
@@ -536,14 +532,14 @@ extern "C" int dwm_add_f32_inplace(void* y, const float* x, int64_t n, void* str
     if (n % 8 != 0 || !dwm_aligned16(x) || !dwm_aligned16(y)) return DWM_EALIGN;
     hipLaunchKernelGGL(add_f32_inplace_kernel, dim3(blocks_for(n / 8)), dim3(256), 0, (hipStream_t)stream,
                        (bf16_t*)y, x, n / 8);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_add_f32_f32_inplace(float* y, const float* x, int64_t n, void* stream) {
     if (x == nullptr || y == nullptr || n <= 0) return DWM_EINVAL;
     if (n % 4 != 0 || !dwm_aligned16(x) || !dwm_aligned16(y)) return DWM_EALIGN;
     hipLaunchKernelGGL(add_f32_f32_inplace_kernel, dim3(blocks_for(n / 4)), dim3(256), 0, (hipStream_t)stream, y, x, n / 4);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_add_inplace(void* y, const void* x, int64_t n, void* stream) {
@@ -551,7 +547,7 @@ extern "C" int dwm_add_inplace(void* y, const void* x, int64_t n, void* stream) 
     if (n % 8 != 0 || !dwm_aligned16(x) || !dwm_aligned16(y)) return DWM_EALIGN;
     hipLaunchKernelGGL(add_inplace_kernel, dim3(blocks_for(n / 8)), dim3(256), 0, (hipStream_t)stream,
                        (bf16_t*)y, (const bf16_t*)x, n / 8);
-    return finish();
+    return dwm_launch_status();
 }
 
 
@@ -608,6 +604,5 @@ extern "C" int dwm_block_permute(const dwm_block_permute_args* a, void* stream) 
     if (nb * chunks >= (1ll << 31)) return DWM_EUNSUPPORTED;
     p.chunks = (uint32_t)chunks;
     hipLaunchKernelGGL(block_permute_kernel, dim3((unsigned)(nb * chunks)), dim3(256), 0, (hipStream_t)stream, p);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DWM_OK : (int)e;
+    return dwm_launch_status();
 }

@@ -11,10 +11,6 @@ using namespace dwm_attn;
 namespace {
 
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
-inline int finish() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DWM_OK : (int)e;
-}
 
 // ---------------------------------------------------------------------------------------------------- LayerNorm family
 // one wave per row, three passes over the row (mean, centred variance, output): the row is re-read from L2
@@ -281,7 +277,7 @@ extern "C" int dwm_layernorm_f32(const dwm_layernorm_args* a, void* stream) {
     if (a->addvec && (a->rows_per_add <= 0 || a->ld_add % 4 != 0 || !dwm_aligned16(a->addvec))) return DWM_EALIGN;
     if (a->xsum && (a->addvec == nullptr || a->ldxsum % 4 != 0 || !dwm_aligned16(a->xsum))) return DWM_EALIGN;
     hipLaunchKernelGGL(layernorm_f32_kernel, dim3((unsigned)((a->rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, *a);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_attention_f32(const dwm_attn_args* a, void* stream) {
@@ -303,20 +299,20 @@ extern "C" int dwm_attention_f32(const dwm_attn_args* a, void* stream) {
         P.seg1_delta = dq;
     }
     hipLaunchKernelGGL(attn_f32_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, P);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_silu_f32(const float* x, float* y, int64_t n, void* stream) {
     if (x == nullptr || y == nullptr || n <= 0) return DWM_EINVAL;
     hipLaunchKernelGGL(silu_f32_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, x, y, n);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_timestep_sinusoid_f32(const float* t, int64_t n, int32_t C, float* out, void* stream) {
     if (t == nullptr || out == nullptr || n <= 0 || C <= 0) return DWM_EINVAL;
     if (C % 2 != 0) return DWM_EUNSUPPORTED;
     hipLaunchKernelGGL(sinusoid_f32_kernel, dim3(blocks_for(n * (C / 2))), dim3(256), 0, (hipStream_t)stream, t, n, C, out);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_patchify_f32(const float* x, int64_t I, int32_t C, int32_t H, int32_t W, int32_t p, float* out, int64_t ldo,
@@ -325,7 +321,7 @@ extern "C" int dwm_patchify_f32(const float* x, int64_t I, int32_t C, int32_t H,
     if (H % p != 0 || W % p != 0 || ldo < (int64_t)C * p * p) return DWM_EINVAL;
     hipLaunchKernelGGL(patchify_f32_kernel, dim3(blocks_for(I * (H / p) * (W / p) * ldo)), dim3(256), 0, (hipStream_t)stream, x, I, C,
                        H, W, p, out, ldo);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_unpatchify_f32(const float* x, int64_t ldx, int64_t I, int32_t C, int32_t h, int32_t w, int32_t p, float* out,
@@ -334,7 +330,7 @@ extern "C" int dwm_unpatchify_f32(const float* x, int64_t ldx, int64_t I, int32_
     if (ldx < (int64_t)C * p * p) return DWM_EINVAL;
     hipLaunchKernelGGL(unpatchify_f32_kernel, dim3(blocks_for(I * C * h * p * w * p)), dim3(256), 0, (hipStream_t)stream, x, ldx, I, C,
                        h, w, p, out);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_cfg_euler_step_f32(const float* pred, float* latents, float* model_in, int64_t n, float guidance, float dsigma,
@@ -343,5 +339,5 @@ extern "C" int dwm_cfg_euler_step_f32(const float* pred, float* latents, float* 
     if (dsigma_group != nullptr && (group_elems <= 0 || n % group_elems != 0)) return DWM_EINVAL;
     hipLaunchKernelGGL(cfg_euler_f32_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, pred, latents, model_in, n, guidance,
                        dsigma, dsigma_group, group_elems > 0 ? group_elems : 1);
-    return finish();
+    return dwm_launch_status();
 }

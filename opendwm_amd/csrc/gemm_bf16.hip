@@ -86,7 +86,25 @@ static inline void set_raster(ConvParams& cp, const dwm_gemm_args& a, int ntn) {
     cp.fd_pergroup = make_fastdiv((uint32_t)(gm * ntn));
     cp.fd_gm = make_fastdiv((uint32_t)gm);
 }
-constexpr int EPI_SPLITK = 100;     // internal epilogue id: fp32 partials to the workspace
+// a dwm_rowmap2d with its divisions prepared (false: not a valid map)
+static inline bool make_dev_rowmap(const dwm_rowmap2d& r, DevRowMap& d) {
+    d.enabled = r.rw > 0;
+    d.xstep = r.xstep > 0 ? (int)r.xstep : 1;
+    if (!d.enabled) { d.rw = make_fastdiv(1); d.rh = make_fastdiv(1); d.rpitch = d.ipitch = d.origin = 0; return true; }
+    if (r.rh <= 0 || r.rw >= (1ll << 30) || r.rh >= (1ll << 30)) return false;
+    d.rw = make_fastdiv((uint32_t)r.rw); d.rh = make_fastdiv((uint32_t)r.rh);
+    d.rpitch = r.rpitch; d.ipitch = r.ipitch; d.origin = r.origin;
+    return true;
+}
+// K steps per tap (256 x 256 x 64 tiles) and the RESID row divisors
+static inline void set_dividers(ConvParams& cp, const dwm_gemm_args& a, int64_t kpt) {
+    cp.steps_per_tap = (int)(kpt / BK);
+    cp.fd_steps = make_fastdiv((uint32_t)cp.steps_per_tap);
+    cp.fd_rpg = make_fastdiv((uint32_t)(a.rows_per_gate > 0 ? a.rows_per_gate : 1));
+    cp.fd_rmod = make_fastdiv((uint32_t)(a.res_mod > 0 ? a.res_mod : a.res_mod < 0 ? -a.res_mod : 1));
+    cp.fd_rpa = make_fastdiv((uint32_t)(a.rows_per_alpha > 0 ? a.rows_per_alpha : 1));
+}
+constexpr int EPI_SPLITK = 100;    // internal epilogue id: fp32 partials to the workspace
 DWM_DEVINL int64_t map_row(const DevRowMap& rm, int64_t m) {
     if (!rm.enabled) return m;
     const uint32_t q = fdiv((uint32_t)m, rm.rw), x = (uint32_t)m - q * rm.rw.d;
@@ -1012,33 +1030,13 @@ extern "C" int dwm_gemm_f32(const dwm_gemm_args* a, void* stream) {
     dwm_gemm_args g = *a;
     g.A = planes; g.lda = kpt;
     ConvParams cp;
-    auto mk = [](const dwm_rowmap2d& r, DevRowMap& d) -> bool {
-        d.enabled = r.rw > 0;
-        d.xstep = r.xstep > 0 ? (int)r.xstep : 1;
-        if (!d.enabled) { d.rw = make_fastdiv(1); d.rh = make_fastdiv(1); d.rpitch = d.ipitch = d.origin = 0; return true; }
-        if (r.rh <= 0 || r.rw >= (1ll << 30) || r.rh >= (1ll << 30)) return false;
-        d.rw = make_fastdiv((uint32_t)r.rw); d.rh = make_fastdiv((uint32_t)r.rh);
-        d.rpitch = r.rpitch; d.ipitch = r.ipitch; d.origin = r.origin;
-        return true;
-    };
-    if (!mk(a->a_map, cp.a) || !mk(a->c_map, cp.c)) return DWM_EINVAL;
-    cp.steps_per_tap = (int)(kpt / BK);
-    cp.fd_steps = make_fastdiv((uint32_t)cp.steps_per_tap);
-    cp.fd_rpg = make_fastdiv((uint32_t)(a->rows_per_gate > 0 ? a->rows_per_gate : 1));
-    cp.fd_rmod = make_fastdiv((uint32_t)(a->res_mod > 0 ? a->res_mod : a->res_mod < 0 ? -a->res_mod : 1));
-    cp.fd_rpa = make_fastdiv((uint32_t)(a->rows_per_alpha > 0 ? a->rows_per_alpha : 1));
+    if (!make_dev_rowmap(a->a_map, cp.a) || !make_dev_rowmap(a->c_map, cp.c)) return DWM_EINVAL;
+    set_dividers(cp, *a, kpt);
     cp.ksplit = ksplit;
     float* const ws_base = (float*)((char*)a->workspace + plane_bytes);
     cp.ws_slice = a->M * a->N;
-    hipError_t e;
-    {
-        static bool attr_set = false;
-        if (!attr_set) {
-            e = hipFuncSetAttribute((const void*)gemm_bf16_kernel<EPI_SPLITK>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-            if (e != hipSuccess) return (int)e;
-            attr_set = true;
-        }
-    }
+    const hipError_t e = dwm_allow_dynamic_lds<gemm_bf16_kernel<EPI_SPLITK>>(LDS_BYTES);
+    if (e != hipSuccess) return (int)e;
     g.reserved = 0;
     for (int gi = 0; gi < ngroups; ++gi) {
         const int tg = gi + 1 < ngroups ? 9 : last_taps;
@@ -1063,8 +1061,7 @@ extern "C" int dwm_gemm_f32(const dwm_gemm_args* a, void* stream) {
         case DWM_EPI_RESID: hipLaunchKernelGGL(f32_finish_kernel<DWM_EPI_RESID>, fg, dim3(256), 0, s, *a, cp); break;
         default: hipLaunchKernelGGL(f32_finish_kernel<DWM_EPI_RMSHEAD>, fg, dim3(256), 0, s, *a, cp); break;
     }
-    e = hipGetLastError();
-    return e == hipSuccess ? DWM_OK : (int)e;
+    return dwm_launch_status();
 }
 
 // gemm_bf16_4w.hip: the 4-wave main loop under the same epilogues (dwm_gemm_args.tile == 3 / 4); -1 = not a launch it covers
@@ -1115,26 +1112,13 @@ extern "C" int dwm_gemm_bf16(const dwm_gemm_args* a_in, void* stream) {
         }
     }
     ConvParams cp;
-    auto mk = [](const dwm_rowmap2d& r, DevRowMap& d) -> bool {
-        d.enabled = r.rw > 0;
-        d.xstep = r.xstep > 0 ? (int)r.xstep : 1;
-        if (!d.enabled) { d.rw = make_fastdiv(1); d.rh = make_fastdiv(1); d.rpitch = d.ipitch = d.origin = 0; return true; }
-        if (r.rh <= 0 || r.rw >= (1ll << 30) || r.rh >= (1ll << 30)) return false;
-        d.rw = make_fastdiv((uint32_t)r.rw); d.rh = make_fastdiv((uint32_t)r.rh);
-        d.rpitch = r.rpitch; d.ipitch = r.ipitch; d.origin = r.origin;
-        return true;
-    };
-    if (!mk(a->a_map, cp.a) || !mk(a->c_map, cp.c)) return DWM_EINVAL;
+    if (!make_dev_rowmap(a->a_map, cp.a) || !make_dev_rowmap(a->c_map, cp.c)) return DWM_EINVAL;
     const int ntaps = a->ntaps > 0 ? a->ntaps : 1;
     if (ntaps > 27) return DWM_EINVAL;
     const int64_t kpt = a->ntaps > 0 ? a->k_per_tap : a->K;
     if (kpt <= 0 || kpt % BK != 0 || kpt * ntaps != a->K) return DWM_EINVAL;
-    cp.steps_per_tap = (int)(kpt / BK);
-    cp.fd_steps = make_fastdiv((uint32_t)cp.steps_per_tap);
     if (a->rows_per_gate > (1ll << 30) || a->res_mod > (1ll << 30) || a->res_mod < -(1ll << 30) || a->rows_per_alpha > (1ll << 30)) return DWM_EINVAL;
-    cp.fd_rpg = make_fastdiv((uint32_t)(a->rows_per_gate > 0 ? a->rows_per_gate : 1));
-    cp.fd_rmod = make_fastdiv((uint32_t)(a->res_mod > 0 ? a->res_mod : a->res_mod < 0 ? -a->res_mod : 1));
-    cp.fd_rpa = make_fastdiv((uint32_t)(a->rows_per_alpha > 0 ? a->rows_per_alpha : 1));
+    set_dividers(cp, *a, kpt);
     for (int t = 0; t < 27; ++t) cp.tap_shift[t] = (a->ntaps > 0 && t < ntaps) ? a->tap_shift[t] : 0;
     if (a->lda < kpt) return DWM_EINVAL;
     if (a->tile < 0 || a->tile > 2) return DWM_EINVAL;
@@ -1170,17 +1154,12 @@ extern "C" int dwm_gemm_bf16(const dwm_gemm_args* a_in, void* stream) {
     cp.ws = (float*)a->workspace;
     cp.ws_slice = a->M * a->N;
     if (ksplit > 1) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            e = hipFuncSetAttribute((const void*)gemm_bf16_kernel<EPI_SPLITK>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-            if (e != hipSuccess) return (int)e;
-            attr_set = true;
-        }
+        e = dwm_allow_dynamic_lds<gemm_bf16_kernel<EPI_SPLITK>>(LDS_BYTES);
+        if (e != hipSuccess) return (int)e;
         hipLaunchKernelGGL(gemm_bf16_kernel<EPI_SPLITK>, dim3((unsigned)(ntm * ntn * ksplit)), dim3(512), LDS_BYTES, s, *a, cp, ntm, ntn);
         const int64_t nthr = a->M * (a->N >> 3);
         hipLaunchKernelGGL(splitk_finish_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, *a, cp);
-        e = hipGetLastError();
-        return e == hipSuccess ? DWM_OK : (int)e;
+        return dwm_launch_status();
     }
     // ---- tile configuration (TileCfg): 256 x 128 tiles (two workgroups per CU) on request, or automatically where they
     // cut the padded columns (N = 320 -> 384 instead of 512: the SD 2.1 UNet's first level) AND K is short, i.e. the
@@ -1202,13 +1181,8 @@ extern "C" int dwm_gemm_bf16(const dwm_gemm_args* a_in, void* stream) {
     const dim3 grid((unsigned)(ntm * ntn)), block(tc == 1 ? TileCfg<1>::nwaves * 64 : 512);
 #define DWM_LAUNCH_TC(EPI, FAST, TC_)                                                                \
     do {                                                                                             \
-        static bool attr_set = false;                                                                \
-        if (!attr_set) {                                                                             \
-            e = hipFuncSetAttribute((const void*)gemm_bf16_kernel<EPI, FAST, false, TC_>,            \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, tile_lds_bytes<TC_>() + (TC_ ? DWM_DEV_LDS_PAD : 0)); \
-            if (e != hipSuccess) return (int)e;                                                      \
-            attr_set = true;                                                                         \
-        }                                                                                            \
+        e = dwm_allow_dynamic_lds<gemm_bf16_kernel<EPI, FAST, false, TC_>>(tile_lds_bytes<TC_>() + (TC_ ? DWM_DEV_LDS_PAD : 0)); \
+        if (e != hipSuccess) return (int)e;                                                          \
         hipLaunchKernelGGL((gemm_bf16_kernel<EPI, FAST, false, TC_>), grid, block,                   \
                            tile_lds_bytes<TC_>() + ((TC_ && (DWM_RESERVED(a->reserved) & 0x400)) ? DWM_DEV_LDS_PAD : 0), s, *a, cp, ntm, ntn); \
     } while (0)
@@ -1228,26 +1202,16 @@ extern "C" int dwm_gemm_bf16(const dwm_gemm_args* a_in, void* stream) {
         if (fast) DWM_LAUNCH(EPI, true); else DWM_LAUNCH(EPI, false);                                \
     } while (0)
     if (a->C32 != nullptr) {                 // fp32 residual stream: RESID with fp32 residual / blend rows and fp32 output
-        static bool attr_set = false;
-        if (!attr_set) {
-            e = hipFuncSetAttribute((const void*)gemm_bf16_kernel<DWM_EPI_RESID, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-            if (e != hipSuccess) return (int)e;
-            e = hipFuncSetAttribute((const void*)gemm_bf16_kernel<DWM_EPI_RESID, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-            if (e != hipSuccess) return (int)e;
-            attr_set = true;
-        }
+        e = dwm_allow_dynamic_lds<gemm_bf16_kernel<DWM_EPI_RESID, false, true>>(LDS_BYTES);
+        if (e == hipSuccess) e = dwm_allow_dynamic_lds<gemm_bf16_kernel<DWM_EPI_RESID, true, true>>(LDS_BYTES);
+        if (e != hipSuccess) return (int)e;
         // the transformer blocks' hidden-state stream takes the FAST form (32-bit row arithmetic, no row map, no activation), and
         // its three operand sets - gate + residual, residual, residual + blend, no bf16 mirror - their compile-time forms (RS)
         const int rs = (a->gate ? 1 : 0) | (a->res ? 2 : 0) | (a->blend ? 4 : 0) | (a->C ? 8 : 0);
 #define DWM_LAUNCH_RS(RS_)                                                                                        \
         do {                                                                                                      \
-            static bool set_ = false;                                                                             \
-            if (!set_) {                                                                                          \
-                e = hipFuncSetAttribute((const void*)gemm_bf16_kernel<DWM_EPI_RESID, true, true, 0, RS_>,         \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);                  \
-                if (e != hipSuccess) return (int)e;                                                               \
-                set_ = true;                                                                                      \
-            }                                                                                                     \
+            e = dwm_allow_dynamic_lds<gemm_bf16_kernel<DWM_EPI_RESID, true, true, 0, RS_>>(LDS_BYTES);            \
+            if (e != hipSuccess) return (int)e;                                                                   \
             hipLaunchKernelGGL((gemm_bf16_kernel<DWM_EPI_RESID, true, true, 0, RS_>), grid, block, LDS_BYTES, s, *a, cp, ntm, ntn); \
         } while (0)
         if (fast && a->ldc32 < lim) {
@@ -1259,20 +1223,14 @@ extern "C" int dwm_gemm_bf16(const dwm_gemm_args* a_in, void* stream) {
             hipLaunchKernelGGL((gemm_bf16_kernel<DWM_EPI_RESID, false, true>), grid, block, LDS_BYTES, s, *a, cp, ntm, ntn);
         }
 #undef DWM_LAUNCH_RS
-        e = hipGetLastError();
-        return e == hipSuccess ? DWM_OK : (int)e;
+        return dwm_launch_status();
     }
     // bf16 RESID, FAST form: the operand sets of the transformer blocks at compile time as well (RS: gate + residual, residual,
     // residual + blend) - the SD 2.1 UNet's K = 320 ... 1280 GEMMs are mostly epilogue
 #define DWM_LAUNCH_RS16(TC_, RS_)                                                                                 \
     do {                                                                                                          \
-        static bool set_ = false;                                                                                 \
-        if (!set_) {                                                                                              \
-            e = hipFuncSetAttribute((const void*)gemm_bf16_kernel<DWM_EPI_RESID, true, false, TC_, RS_>,          \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, tile_lds_bytes<TC_>() + (TC_ ? DWM_DEV_LDS_PAD : 0)); \
-            if (e != hipSuccess) return (int)e;                                                                   \
-            set_ = true;                                                                                          \
-        }                                                                                                         \
+        e = dwm_allow_dynamic_lds<gemm_bf16_kernel<DWM_EPI_RESID, true, false, TC_, RS_>>(tile_lds_bytes<TC_>() + (TC_ ? DWM_DEV_LDS_PAD : 0)); \
+        if (e != hipSuccess) return (int)e;                                                                       \
         hipLaunchKernelGGL((gemm_bf16_kernel<DWM_EPI_RESID, true, false, TC_, RS_>), grid, block,                 \
                            tile_lds_bytes<TC_>() + ((TC_ && (DWM_RESERVED(a->reserved) & 0x400)) ? DWM_DEV_LDS_PAD : 0), s, *a, cp, ntm, ntn); \
     } while (0)
@@ -1296,6 +1254,5 @@ extern "C" int dwm_gemm_bf16(const dwm_gemm_args* a_in, void* stream) {
 #undef DWM_LAUNCH2
 #undef DWM_LAUNCH
 #undef DWM_LAUNCH_TC
-    e = hipGetLastError();
-    return e == hipSuccess ? DWM_OK : (int)e;
+    return dwm_launch_status();
 }

@@ -468,17 +468,12 @@ std::atomic<int64_t> g_launches_gen{0};
 
 template <int EPI, bool RF32, int RS, bool GEN = false>
 int launch4w(const dwm_gemm_args* a, const G4Params& gp, hipStream_t s) {
-    static bool attr = false;
-    if (!attr) {
-        const hipError_t e = hipFuncSetAttribute((const void*)gemm4w_kernel<EPI, RF32, RS, GEN>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        attr = true;
-    }
+    const hipError_t e = dwm_allow_dynamic_lds<gemm4w_kernel<EPI, RF32, RS, GEN>>(LDS_BYTES);
+    if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL((gemm4w_kernel<EPI, RF32, RS, GEN>), dim3((unsigned)(gp.ntm * gp.ntn)), dim3(256), LDS_BYTES, s, *a, gp);
     g_launches.fetch_add(1, std::memory_order_relaxed);
     if (GEN) g_launches_gen.fetch_add(1, std::memory_order_relaxed);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DWM_OK : (int)e;
+    return dwm_launch_status();
 }
 
 }  // namespace

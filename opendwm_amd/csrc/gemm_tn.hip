@@ -255,11 +255,7 @@ extern "C" int dwm_gemm_tn(const dwm_gemm_tn_args* a, void* stream) {
     if (kmax < 1) return DWM_EINVAL;
     int ksplit = a->split_k;
     if (ksplit <= 0) {
-        static int ncu = 0;
-        if (ncu == 0) {
-            int dev = 0;
-            if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-        }
+        const int ncu = dwm_cu_count();
         double best = 0.0;
         for (int k = 1; k <= kmax; ++k) {
             const int64_t rounds = (tiles * k + ncu - 1) / ncu;
@@ -274,19 +270,11 @@ extern "C" int dwm_gemm_tn(const dwm_gemm_tn_args* a, void* stream) {
     p.ws = (float*)a->workspace;
     p.ws_slice = slice_floats;
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e;
-    {
-        static bool attr_set = false;
-        if (!attr_set) {
-            e = hipFuncSetAttribute((const void*)gemm_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS);
-            if (e != hipSuccess) return (int)e;
-            attr_set = true;
-        }
-    }
+    const hipError_t e = dwm_allow_dynamic_lds<gemm_tn_kernel>(TN_LDS);
+    if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(gemm_tn_kernel, dim3((unsigned)(tiles * ksplit)), dim3(512), TN_LDS, s, p);
     const int64_t nthr = a->N * (((int64_t)ntaps * a->C) >> 3);
     hipLaunchKernelGGL(tn_finish_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, p.ws, p.ws_slice, ksplit, a->N,
                        (int64_t)ntaps * a->C, (bf16_t*)a->out, a->ldo);
-    e = hipGetLastError();
-    return e == hipSuccess ? DWM_OK : (int)e;
+    return dwm_launch_status();
 }

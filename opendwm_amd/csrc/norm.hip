@@ -172,8 +172,7 @@ static int layernorm_launch(const dwm_layernorm_args* a, void* stream, bool x32)
             default: hipLaunchKernelGGL((layernorm_kernel<4, false>), grid, block, 0, s, *a); break;
         }
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DWM_OK : (int)e;
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_layernorm(const dwm_layernorm_args* a, void* stream) { return layernorm_launch(a, stream, false); }
@@ -187,6 +186,5 @@ extern "C" int dwm_rmsnorm_heads(void* x, int64_t ldx, int64_t rows, int64_t nco
     const int64_t nthreads = rows * nheads * 8;
     hipLaunchKernelGGL(rmsnorm_heads_kernel, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, (bf16_t*)x, ldx, rows, nheads, (const bf16_t*)w, eps);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DWM_OK : (int)e;
+    return dwm_launch_status();
 }

@@ -519,11 +519,6 @@ inline unsigned grid_for(int64_t work_items) {
 
 }  // namespace
 
-#define DWM_RET()                                          \
-    do {                                                   \
-        const hipError_t e_ = hipGetLastError();           \
-        return e_ == hipSuccess ? DWM_OK : (int)e_;        \
-    } while (0)
 
 extern "C" int dwm_transpose_bf16(const void* in, int64_t ld_in, int64_t rows, int64_t cols, void* out,
                                   int64_t ld_out, int64_t rows_pad, void* stream) {
@@ -532,12 +527,12 @@ extern "C" int dwm_transpose_bf16(const void* in, int64_t ld_in, int64_t rows, i
         const dim3 grid8((unsigned)((cols + 127) / 128), (unsigned)((rows_pad + 127) / 128));
         hipLaunchKernelGGL(transpose8_kernel, grid8, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)in, ld_in, rows, cols,
                            (bf16_t*)out, ld_out, rows_pad);
-        DWM_RET();
+        return dwm_launch_status();
     }
     const dim3 grid((unsigned)((cols + 63) / 64), (unsigned)((rows_pad + 63) / 64));
     hipLaunchKernelGGL(transpose_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)in, ld_in, rows, cols,
                        (bf16_t*)out, ld_out, rows_pad);
-    DWM_RET();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_segsum(const void* a, int64_t lda, const void* b, int64_t ldb, int64_t rows, int64_t ncols,
@@ -551,7 +546,7 @@ extern "C" int dwm_segsum(const void* a, int64_t lda, const void* b, int64_t ldb
     const dim3 grid((unsigned)((ncols + 255) / 256), (unsigned)(groups * cpg));
     hipLaunchKernelGGL(segsum_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, lda, (const bf16_t*)b, ldb,
                        (const bf16_t*)nullptr, (int64_t)0, rows, ncols, rows_per_group, cpg, out, ld_out);
-    DWM_RET();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_segsum_diff(const void* a, int64_t lda, const void* b, int64_t ldb, const void* b2, int64_t ldb2, int64_t rows,
@@ -565,7 +560,7 @@ extern "C" int dwm_segsum_diff(const void* a, int64_t lda, const void* b, int64_
     const dim3 grid((unsigned)((ncols + 255) / 256), (unsigned)(groups * cpg));
     hipLaunchKernelGGL(segsum_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, lda, (const bf16_t*)b, ldb,
                        (const bf16_t*)b2, ldb2, rows, ncols, rows_per_group, cpg, out, ld_out);
-    DWM_RET();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_act_fwd(const void* x, void* y, int64_t n, int32_t act, void* stream) {
@@ -576,7 +571,7 @@ extern "C" int dwm_act_fwd(const void* x, void* y, int64_t n, int32_t act, void*
     else if (act == DWM_ACT_SILU) hipLaunchKernelGGL((act_kernel<DWM_ACT_SILU, false>), dim3(grid_for(n / 8)), dim3(256), 0, s, (const bf16_t*)x, nullptr, (bf16_t*)y, n / 8);
     else if (act == DWM_ACT_RELU) hipLaunchKernelGGL((act_kernel<DWM_ACT_RELU, false>), dim3(grid_for(n / 8)), dim3(256), 0, s, (const bf16_t*)x, nullptr, (bf16_t*)y, n / 8);
     else return DWM_EINVAL;
-    DWM_RET();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_act_bwd(const void* x, const void* dy, void* dx, int64_t n, int32_t act, void* stream) {
@@ -587,7 +582,7 @@ extern "C" int dwm_act_bwd(const void* x, const void* dy, void* dx, int64_t n, i
     else if (act == DWM_ACT_SILU) hipLaunchKernelGGL((act_kernel<DWM_ACT_SILU, true>), dim3(grid_for(n / 8)), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, n / 8);
     else if (act == DWM_ACT_RELU) hipLaunchKernelGGL((act_kernel<DWM_ACT_RELU, true>), dim3(grid_for(n / 8)), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, n / 8);
     else return DWM_EINVAL;
-    DWM_RET();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_geglu_fwd(const void* u, int64_t ldu, int64_t rows, int64_t inner, void* g, int64_t ldg, void* stream) {
@@ -595,7 +590,7 @@ extern "C" int dwm_geglu_fwd(const void* u, int64_t ldu, int64_t rows, int64_t i
     if (ldu % 8 != 0 || ldg % 8 != 0 || !dwm_aligned16(u) || !dwm_aligned16(g)) return DWM_EALIGN;
     hipLaunchKernelGGL((geglu_kernel<false>), dim3(grid_for(rows * inner / 8)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)u, ldu, nullptr, 0, (bf16_t*)g, ldg, rows, inner);
-    DWM_RET();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_geglu_bwd(const void* u, int64_t ldu, const void* dg, int64_t lddg, int64_t rows, int64_t inner,
@@ -604,7 +599,7 @@ extern "C" int dwm_geglu_bwd(const void* u, int64_t ldu, const void* dg, int64_t
     if (ldu % 8 != 0 || lddg % 8 != 0 || lddu % 8 != 0 || !dwm_aligned16(u) || !dwm_aligned16(dg) || !dwm_aligned16(du)) return DWM_EALIGN;
     hipLaunchKernelGGL((geglu_kernel<true>), dim3(grid_for(rows * inner / 8)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)u, ldu, (const bf16_t*)dg, lddg, (bf16_t*)du, lddu, rows, inner);
-    DWM_RET();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_rowcombine(const dwm_rowcombine_args* a, void* stream) {
@@ -616,7 +611,7 @@ extern "C" int dwm_rowcombine(const dwm_rowcombine_args* a, void* stream) {
                        (const bf16_t*)a->a, a->lda, (const bf16_t*)a->gate_a, a->ld_gate_a, a->rows_per_gate_a,
                        a->coef_a, a->rows_per_coef_a, (const bf16_t*)a->b, a->ldb, a->coef_b, a->rows_per_coef_b,
                        (bf16_t*)a->out, a->ldo, a->rows, a->ncols);
-    DWM_RET();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_layernorm_bwd(const dwm_layernorm_bwd_args* a, void* stream) {
@@ -638,7 +633,7 @@ extern "C" int dwm_layernorm_bwd(const dwm_layernorm_bwd_args* a, void* stream) 
         case 3: hipLaunchKernelGGL(layernorm_bwd_kernel<3>, grid, dim3(256), 0, s, *a, cpg); break;
         default: hipLaunchKernelGGL(layernorm_bwd_kernel<4>, grid, dim3(256), 0, s, *a, cpg); break;
     }
-    DWM_RET();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_rmsnorm_heads_train(void* x, int64_t ldx, int64_t rows, int64_t ncols, const void* w, float eps,
@@ -647,7 +642,7 @@ extern "C" int dwm_rmsnorm_heads_train(void* x, int64_t ldx, int64_t rows, int64
     if (!dwm_aligned16(x) || !dwm_aligned16(w)) return DWM_EALIGN;
     hipLaunchKernelGGL(rmsnorm_heads_train_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                        (bf16_t*)x, ldx, rows, ncols, (const bf16_t*)w, eps, rinv);
-    DWM_RET();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_rmsnorm_heads_bwd(const void* y, int64_t ldy, const float* rinv, const void* w, void* dy, int64_t lddy,
@@ -656,7 +651,7 @@ extern "C" int dwm_rmsnorm_heads_bwd(const void* y, int64_t ldy, const float* ri
     if (ldy % 8 != 0 || lddy % 8 != 0 || !dwm_aligned16(y) || !dwm_aligned16(dy) || !dwm_aligned16(w)) return DWM_EALIGN;
     hipLaunchKernelGGL(rmsnorm_heads_bwd_kernel, dim3((unsigned)((rows + 31) / 32)), dim3(256), (size_t)ncols * sizeof(float),
                        (hipStream_t)stream, (const bf16_t*)y, ldy, rinv, (const bf16_t*)w, (bf16_t*)dy, lddy, rows, ncols, dw);
-    DWM_RET();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_adamw(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1,
@@ -665,7 +660,7 @@ extern "C" int dwm_adamw(float* p, const float* g, float* m, float* v, void* p_b
     if (!p || !g || !m || !v || n <= 0 || bias_corr1 <= 0.f || bias_corr2 <= 0.f) return DWM_EINVAL;
     hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16, n, lr,
                        beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale);
-    DWM_RET();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_adamw_multi(const dwm_adamw_item* items, const int32_t* block_item, const int64_t* block_start, int64_t n_blocks,
@@ -675,7 +670,7 @@ extern "C" int dwm_adamw_multi(const dwm_adamw_item* items, const int32_t* block
         bias_corr2 <= 0.f) return DWM_EINVAL;
     hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, items, block_item, block_start,
                        chunk, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale);
-    DWM_RET();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_cast_bf16_to_f32(const void* x, int64_t ldx, float* y, int64_t ldy, int64_t rows, int64_t cols,
@@ -687,5 +682,5 @@ extern "C" int dwm_cast_bf16_to_f32(const void* x, int64_t ldx, float* y, int64_
     else
         hipLaunchKernelGGL(cast_bf16_to_f32_kernel, dim3(grid_for(rows * cols)), dim3(256), 0, (hipStream_t)stream,
                            (const bf16_t*)x, ldx, y, ldy, rows, cols, accumulate);
-    DWM_RET();
+    return dwm_launch_status();
 }

@@ -395,10 +395,6 @@ gn_bwd_apply_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dz,
     *(uint4*)(dx + r * C + c8 * 8) = pack8(o);
 }
 
-inline int finish() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DWM_OK : (int)e;
-}
 
 }  // namespace
 
@@ -471,7 +467,7 @@ static int groupnorm_impl(const void* x, void* y, int64_t I, int64_t P, int32_t 
         else
             hipLaunchKernelGGL(gn_spatial_apply_kernel<bf16_t>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const bf16_t*)x,
                                (bf16_t*)y, I, P, C, G, stats, (const bf16_t*)gamma, (const bf16_t*)beta, eps, silu, pm, im, zm);
-        return finish();
+        return dwm_launch_status();
     }
     if (f32)
         hipLaunchKernelGGL(gn_apply_kernel<float>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)x,
@@ -479,7 +475,7 @@ static int groupnorm_impl(const void* x, void* y, int64_t I, int64_t P, int32_t 
     else
         hipLaunchKernelGGL(gn_apply_kernel<bf16_t>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const bf16_t*)x,
                            (bf16_t*)y, I, P, C, G, stats, (const bf16_t*)gamma, (const bf16_t*)beta, eps, silu, pm, im);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_groupnorm_bwd(const void* x, const void* dz, void* dx, int64_t I, int64_t P, int32_t C, int32_t G, float eps,
@@ -533,7 +529,7 @@ extern "C" int dwm_groupnorm_bwd(const void* x, const void* dz, void* dx, int64_
     hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)dz,
                        (bf16_t*)dx, I, P, C, G, (const float*)fstats, (const float*)bstats, (const bf16_t*)gamma, (const bf16_t*)beta,
                        eps, silu, accumulate, pm, im);
-    return finish();
+    return dwm_launch_status();
 }
 
 extern "C" int dwm_groupnorm_silu_mapped(const void* x, void* y, int64_t I, int64_t P, int32_t C, int32_t G, float eps,
@@ -580,7 +576,7 @@ static int frame_mix_impl(const void* x, void* y, int64_t frame_elems, const dwm
     const dim3 grid((unsigned)((fe8 + 255) / 256), (unsigned)mix->n_out);
     if (f32) hipLaunchKernelGGL(frame_mix_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)x, (float*)y, fe8, fm);
     else hipLaunchKernelGGL(frame_mix_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, fe8, fm);
-    return finish();
+    return dwm_launch_status();
 }
 extern "C" int dwm_frame_mix_bf16(const void* x, void* y, int64_t frame_elems, const dwm_frame_mix* mix, void* stream) {
     return frame_mix_impl(x, y, frame_elems, mix, stream, false);
@@ -603,7 +599,7 @@ static int upsample2_impl(const void* x, void* y, int64_t I, int32_t h, int32_t 
     const dim3 grid((unsigned)((total + 255) / 256));
     if (f32) hipLaunchKernelGGL(upsample2_pad_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)x, (float*)y, I, h, w, C / 8);
     else hipLaunchKernelGGL(upsample2_pad_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, I, h, w, C / 8);
-    return finish();
+    return dwm_launch_status();
 }
 extern "C" int dwm_upsample2_padded(const void* x, void* y, int64_t I, int32_t h, int32_t w, int32_t C, void* stream) {
     return upsample2_impl(x, y, I, h, w, C, stream, false);
@@ -624,7 +620,7 @@ static int softmax_rows_impl(const T* x, T* y, int64_t rows, int32_t L, int64_t 
     if (ni <= 2) hipLaunchKernelGGL((softmax_rows_kernel<2, T>), grid, block, 0, s, x, y, rows, L, ld, sl);
     else if (ni <= 4) hipLaunchKernelGGL((softmax_rows_kernel<4, T>), grid, block, 0, s, x, y, rows, L, ld, sl);
     else hipLaunchKernelGGL((softmax_rows_kernel<8, T>), grid, block, 0, s, x, y, rows, L, ld, sl);
-    return finish();
+    return dwm_launch_status();
 }
 extern "C" int dwm_softmax_rows(const void* x, void* y, int64_t rows, int32_t L, int64_t ld, float scale, void* stream) {
     return softmax_rows_impl<bf16_t>((const bf16_t*)x, (bf16_t*)y, rows, L, ld, scale, stream);
@@ -652,5 +648,5 @@ static int pad_tokens_impl(const void* x, void* y, int64_t rows, int32_t C, cons
     const dim3 grid((unsigned)((total + 255) / 256));
     if (f32) hipLaunchKernelGGL(pad_tokens_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)x, (float*)y, rows, C / 8, pm);
     else hipLaunchKernelGGL(pad_tokens_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, rows, C / 8, pm);
-    return finish();
+    return dwm_launch_status();
 }
