@@ -18,10 +18,21 @@ from ._lib import (ACT_GELU_TANH, ACT_NONE, ACT_RELU, ACT_SILU, EPI_GEGLU, EPI_P
 
 BIG = 1 << 30
 bf16 = torch.bfloat16
+f32 = torch.float32
 
 
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
+
+
+def _call(name: str, *args) -> None:
+    """run entry point `name` (a key of _lib.SIGNATURES) on the current stream; a failure is reported under that name"""
+    _lib.check(getattr(_lib.load(), name)(*args, _stream()), name)
+
+
+def _dt(t: torch.Tensor):
+    """dtype a wrapper expects of its tensors, chosen by its first one: fp32 = the accuracy path, anything else must be bf16"""
+    return f32 if t.dtype == f32 else bf16
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -166,6 +177,83 @@ def _overlaps(a: torch.Tensor, b: torch.Tensor) -> bool:
     return a0 < b1 and b0 < a1
 
 
+def _gemm_dims(a, w, dt, rows, epilogue, a_grid, conv3x3, stride2, conv_taps, c_grid, fp32_checks):
+    """operand checks and the (M, N, K, taps, nout, orow) of a dwm_gemm_args: M output pixels, `taps` K-axis taps, out [orow, nout]"""
+    _chk2d(a, "a", dt)
+    _chk2d(w, "w", dt)
+    if not w.is_contiguous():
+        raise RuntimeError("w must be contiguous [N, K]")
+    N, K = w.shape
+    taps = 9 if conv3x3 else len(conv_taps) if conv_taps is not None else 1
+    # known asymmetry: dwm_gemm_f32's wrapper makes three checks (fp32_checks) that dwm_gemm_bf16's never made; kept as they were
+    if fp32_checks and taps > 27:
+        raise NotImplementedError("gemm (fp32): at most 27 taps (three groups of 9, each tap walked as three plane products)")
+    if a_grid is not None:
+        if a.shape[0] != a_grid.rows or a.shape[1] * taps != K or (fp32_checks and not a.is_contiguous()):
+            raise RuntimeError(f"gemm: padded A {tuple(a.shape)} does not match grid / weight {tuple(w.shape)}")
+        if stride2 and (not conv3x3 or a_grid.h % 2 or a_grid.w % 2):
+            raise RuntimeError("gemm: stride2 needs conv3x3 on an even-sized grid")
+        M = a_grid.pixels // 4 if stride2 else a_grid.pixels
+    else:
+        if fp32_checks and (conv3x3 or conv_taps is not None or stride2):
+            raise RuntimeError("gemm: convolution taps need a_grid")
+        M = a.shape[0] if rows is None else rows
+        if a.shape[1] != K:
+            raise RuntimeError(f"gemm: K mismatch {a.shape} x {w.shape}")
+    if c_grid is not None and c_grid.pixels != M:
+        raise RuntimeError("gemm: c_grid pixel count != M")
+    return M, N, K, taps, N // 2 if epilogue == EPI_GEGLU else N, c_grid.rows if c_grid is not None else M
+
+
+def _gemm_out(out, shape, dt, device, padded):
+    """the [orow, nout] result matrix: allocated (zeroed when it is a padded grid, whose border the kernel leaves alone) or checked"""
+    if out is None:
+        out = (torch.zeros if padded else torch.empty)(shape, dtype=dt, device=device)
+    _chk2d(out, "out", dt)
+    if out.shape != shape:
+        raise RuntimeError(f"gemm: out shape {tuple(out.shape)} != {shape}")
+    return out
+
+
+def _gemm_operands(g, dt, stream_dt, gate, rows_per_gate, res, res_mod, blend, alpha, rows_per_alpha, rms_w, rms_ncols, rms_eps):
+    """the epilogue operands of a dwm_gemm_args.  dt: dtype of gate / rms_w; stream_dt: dtype of res / blend (fp32 where the bf16
+    GEMM updates the fp32 residual stream)"""
+    if gate is not None:
+        _chk2d(gate, "gate", dt)
+        g.gate, g.ld_gate, g.rows_per_gate = gate.data_ptr(), gate.stride(0), rows_per_gate
+    if res is not None:
+        _chk2d(res, "res", stream_dt)
+        g.res, g.ld_res, g.res_mod = res.data_ptr(), res.stride(0), res_mod
+    if blend is not None:
+        _chk2d(blend, "blend", stream_dt)
+        _chkvec(alpha, "alpha", f32)
+        g.blend, g.ld_blend, g.alpha, g.rows_per_alpha = blend.data_ptr(), blend.stride(0), alpha.data_ptr(), rows_per_alpha
+    if rms_w is not None:
+        _chkvec(rms_w, "rms_w", dt)
+        g.rms_w, g.rms_ncols, g.rms_eps = rms_w.data_ptr(), rms_ncols, rms_eps
+
+
+def _gemm_maps(g, a, a_grid, conv3x3, stride2, conv_taps, c_grid, res, blend):
+    """a_map, the taps and c_map of a dwm_gemm_args whose A / out (with res, blend) are padded token grids"""
+    if a_grid is not None:
+        if stride2:
+            (a_grid.fill_stride2_sym if stride2 == "sym" else a_grid.fill_stride2)(g.a_map)
+        else:
+            a_grid.fill(g.a_map)
+        shifts = conv_taps
+        if conv3x3:
+            shifts = a_grid.tap_shifts_stride2() if stride2 else a_grid.tap_shifts()
+        if shifts is not None:
+            g.ntaps, g.k_per_tap = len(shifts), a.shape[1]
+            for t, sh in enumerate(shifts):
+                g.tap_shift[t] = sh
+    if c_grid is not None:
+        c_grid.fill(g.c_map)
+        for name, t in (("res", res), ("blend", blend)):
+            if t is not None and t.shape[0] != c_grid.rows:
+                raise RuntimeError(f"gemm: {name} must be a padded grid when c_grid is given")
+
+
 def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *,
          out: Optional[torch.Tensor] = None, epilogue: int = EPI_PLAIN, act: int = ACT_NONE,
          gate: Optional[torch.Tensor] = None, rows_per_gate: int = 1,
@@ -185,40 +273,18 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
     out32 (RESID): fp32 residual stream - `res` and `blend` are then fp32 matrices shaped like the output, the result goes to
     out32 in fp32 (out32 may be `res` or `blend` itself) and, rounded, to the bf16 `out`; mirror=False: no bf16 copy at all
     (`out` must be None; the call returns out32) - the hidden / context streams of the bf16 MMDiT forward.
-    w_is_activation: `w` is a per-call tensor, not a parameter (fp32 path: its operand planes are not cached)."""
-    if a.dtype == torch.float32:            # the fp32 accuracy path (dwm_gemm_f32)
-        return _gemm_f32(a, w, bias, out=out, epilogue=epilogue, act=act, gate=gate, rows_per_gate=rows_per_gate, res=res,
-                         res_mod=res_mod, blend=blend, alpha=alpha, rows_per_alpha=rows_per_alpha, rms_w=rms_w,
-                         rms_ncols=rms_ncols, rms_eps=rms_eps, rows=rows, a_grid=a_grid, conv3x3=conv3x3, c_grid=c_grid,
-                         stride2=stride2, conv_taps=conv_taps, cache_w=not w_is_activation)
-    _chk2d(a, "a")
-    _chk2d(w, "w")
-    if not w.is_contiguous():
-        raise RuntimeError("w must be contiguous [N, K]")
-    N, K = w.shape
-    if a_grid is not None:
-        ntap_ = 9 if conv3x3 else (len(conv_taps) if conv_taps is not None else 1)
-        if a.shape[0] != a_grid.rows or a.shape[1] * ntap_ != K:
-            raise RuntimeError(f"gemm: padded A {tuple(a.shape)} does not match grid / weight {tuple(w.shape)}")
-        M = a_grid.pixels // 4 if stride2 else a_grid.pixels
-    else:
-        M = a.shape[0] if rows is None else rows
-        if a.shape[1] != K:
-            raise RuntimeError(f"gemm: K mismatch {a.shape} x {w.shape}")
-    nout = N // 2 if epilogue == EPI_GEGLU else N
-    orow = c_grid.rows if c_grid is not None else M
-    if c_grid is not None and c_grid.pixels != M:
-        raise RuntimeError("gemm: c_grid pixel count != M")
+    w_is_activation: `w` is a per-call tensor, not a parameter (fp32 path: its operand planes are not cached).
+    fp32 `a`: the accuracy path (dwm_gemm_f32), all operands fp32; out32, mirror, split_k, tile and _debug are not looked at."""
+    if a.dtype == f32:
+        return _gemm_f32(a, w, bias, out, rows, epilogue, act, gate, rows_per_gate, res, res_mod, blend, alpha, rows_per_alpha, rms_w,
+                         rms_ncols, rms_eps, a_grid, conv3x3, stride2, conv_taps, c_grid, not w_is_activation)
+    M, N, K, _, nout, orow = _gemm_dims(a, w, bf16, rows, epilogue, a_grid, conv3x3, stride2, conv_taps, c_grid, False)
     if not mirror:
         if out32 is None or out is not None:
             raise RuntimeError("gemm: mirror=False needs out32 and no `out`")
     else:
-        if out is None:
-            out = (torch.zeros if c_grid is not None else torch.empty)((orow, nout), dtype=bf16, device=a.device)
-        _chk2d(out, "out")
-        if out.shape != (orow, nout):
-            raise RuntimeError(f"gemm: out shape {tuple(out.shape)} != {(orow, nout)}")
-        if _overlaps(a, out):
+        out = _gemm_out(out, (orow, nout), bf16, a.device, c_grid is not None)
+        if _overlaps(a, out):       # bf16 only (like the three checks of _gemm_dims, an asymmetry kept as it was)
             raise RuntimeError("gemm: `out` overlaps the A operand (a tile's output would overwrite rows other tiles still read)")
     _chkvec(bias, "bias")
     g = _lib.GemmArgs()
@@ -226,60 +292,27 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
     if out is not None:
         g.C, g.ldc = out.data_ptr(), out.stride(0)
     g.M, g.N, g.K, g.epilogue, g.act = M, N, K, epilogue, act
-    if gate is not None:
-        _chk2d(gate, "gate")
-        g.gate, g.ld_gate, g.rows_per_gate = gate.data_ptr(), gate.stride(0), rows_per_gate
-    if out32 is not None:
+    if out32 is not None:           # the fp32-stream form: res / blend are fp32 and shaped like out32, no split-K
         if epilogue != EPI_RESID or res_mod != 0:
             raise RuntimeError("gemm: out32 needs the RESID epilogue (res_mod = 0; `res`, if any, in fp32)")
-        _chk2d(out32, "out32", torch.float32)
+        _chk2d(out32, "out32", f32)
         if out32.shape != (orow, nout):
             raise RuntimeError("gemm: out32 must have the shape of the output")
-        if res is not None:
-            _chk2d(res, "res", torch.float32)
-            if res.shape != out32.shape:
-                raise RuntimeError("gemm: the fp32 res must have the shape of the output")
-            g.res, g.ld_res, g.res_mod = res.data_ptr(), res.stride(0), 0
+        if res is not None and res.shape != out32.shape:
+            raise RuntimeError("gemm: the fp32 res must have the shape of the output")
         g.C32, g.ldc32 = out32.data_ptr(), out32.stride(0)
         split_k = 1
-    elif res is not None:
-        _chk2d(res, "res")
-        g.res, g.ld_res, g.res_mod = res.data_ptr(), res.stride(0), res_mod
-    if blend is not None:
-        _chk2d(blend, "blend", torch.float32 if out32 is not None else bf16)
-        _chkvec(alpha, "alpha", torch.float32)
-        g.blend, g.ld_blend, g.alpha, g.rows_per_alpha = blend.data_ptr(), blend.stride(0), alpha.data_ptr(), rows_per_alpha
-    if rms_w is not None:
-        _chkvec(rms_w, "rms_w")
-        g.rms_w, g.rms_ncols, g.rms_eps = rms_w.data_ptr(), rms_ncols, rms_eps
-    if a_grid is not None:
-        if stride2:
-            if not conv3x3 or a_grid.h % 2 or a_grid.w % 2:
-                raise RuntimeError("gemm: stride2 needs conv3x3 on an even-sized grid")
-            (a_grid.fill_stride2_sym if stride2 == "sym" else a_grid.fill_stride2)(g.a_map)
-        else:
-            a_grid.fill(g.a_map)
-        if conv3x3:
-            g.ntaps, g.k_per_tap = 9, a.shape[1]
-            for t, sh in enumerate(a_grid.tap_shifts_stride2() if stride2 else a_grid.tap_shifts()):
-                g.tap_shift[t] = sh
-        elif conv_taps is not None:
-            g.ntaps, g.k_per_tap = len(conv_taps), a.shape[1]
-            for t, sh in enumerate(conv_taps):
-                g.tap_shift[t] = sh
-    if c_grid is not None:
-        c_grid.fill(g.c_map)
-        for name, t in (("res", res), ("blend", blend)):
-            if t is not None and t.shape[0] != c_grid.rows:
-                raise RuntimeError(f"gemm: {name} must be a padded grid when c_grid is given")
+    _gemm_operands(g, bf16, f32 if out32 is not None else bf16, gate, rows_per_gate, res, res_mod, blend, alpha, rows_per_alpha,
+                   rms_w, rms_ncols, rms_eps)
+    _gemm_maps(g, a, a_grid, conv3x3, stride2, conv_taps, c_grid, res, blend)
     g.reserved = _debug
     g.split_k = split_k
     g.tile = _gemm_tile_request(tile)
-    # split-K scratch (fp32 partial tiles): only handed over when the kernel's own rule can take it
+    # split-K scratch (fp32 partial tiles, a fixed 1 GiB): only handed over when the kernel's own rule can take it
     if split_k != 1 and epilogue in (EPI_PLAIN, EPI_RESID) and ((M + 255) // 256) * ((N + 255) // 256) <= 128 and K >= 1024:
         ws = _gemm_workspace(a.device)
         g.workspace, g.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-    _lib.check(_lib.load().dwm_gemm_bf16(C.byref(g), _stream()), "dwm_gemm_bf16")
+    _call("dwm_gemm_bf16", C.byref(g))
     return out if mirror else out32
 
 
@@ -308,7 +341,7 @@ def block_permute(src: torch.Tensor, dst: torch.Tensor, dims, src_strides, block
         n *= dims[i]
     if n * block_elems != src.numel() or dst.numel() != src.numel():
         raise RuntimeError("block_permute: dims x block size do not cover the tensors")
-    _lib.check(_lib.load().dwm_block_permute(C.byref(a), _stream()), "dwm_block_permute")
+    _call("dwm_block_permute", C.byref(a))
     return dst
 
 
@@ -408,110 +441,55 @@ def clear_split_weights() -> None:
     _SPLIT_WEIGHTS.clear()
 
 
-def _gemm_f32(a, w, bias, *, out, epilogue, act, gate, rows_per_gate, res, res_mod, blend, alpha, rows_per_alpha, rms_w, rms_ncols,
-              rms_eps, rows, a_grid=None, conv3x3=False, c_grid=None, stride2=False, conv_taps=None, cache_w=True):
-    f32 = torch.float32
-    _chk2d(a, "a", f32)
-    _chk2d(w, "w", f32)
-    if not w.is_contiguous():
-        raise RuntimeError("w must be contiguous [N, K]")
-    N, K = w.shape
-    taps = 9 if conv3x3 else len(conv_taps) if conv_taps is not None else 1
-    if taps > 27:
-        raise NotImplementedError("gemm (fp32): at most 27 taps (three groups of 9, each tap walked as three plane products)")
-    if a_grid is not None:
-        if a.shape[0] != a_grid.rows or a.shape[1] * taps != K or not a.is_contiguous():
-            raise RuntimeError(f"gemm: padded A {tuple(a.shape)} does not match grid / weight {tuple(w.shape)}")
-        if stride2 and (not conv3x3 or a_grid.h % 2 or a_grid.w % 2):
-            raise RuntimeError("gemm: stride2 needs conv3x3 on an even-sized grid")
-        M, a_rows = (a_grid.pixels // 4 if stride2 else a_grid.pixels), a_grid.rows
-    else:
-        if conv3x3 or conv_taps is not None or stride2:
-            raise RuntimeError("gemm: convolution taps need a_grid")
-        M = a.shape[0] if rows is None else rows
-        a_rows = M
-        if a.shape[1] != K:
-            raise RuntimeError(f"gemm: K mismatch {a.shape} x {w.shape}")
-    nout = N // 2 if epilogue == EPI_GEGLU else N
-    orow = c_grid.rows if c_grid is not None else M
-    if c_grid is not None and c_grid.pixels != M:
-        raise RuntimeError("gemm: c_grid pixel count != M")
-    if out is None:
-        out = (torch.zeros if c_grid is not None else torch.empty)((orow, nout), dtype=f32, device=a.device)
-    _chk2d(out, "out", f32)
-    if out.shape != (orow, nout):
-        raise RuntimeError(f"gemm: out shape {tuple(out.shape)} != {(orow, nout)}")
+def _gemm_f32(a, w, bias, out, rows, epilogue, act, gate, rows_per_gate, res, res_mod, blend, alpha, rows_per_alpha, rms_w, rms_ncols,
+              rms_eps, a_grid, conv3x3, stride2, conv_taps, c_grid, cache_w):
+    """gemm() for fp32 operands (dwm_gemm_f32)"""
+    M, N, K, taps, nout, orow = _gemm_dims(a, w, f32, rows, epilogue, a_grid, conv3x3, stride2, conv_taps, c_grid, True)
+    out = _gemm_out(out, (orow, nout), f32, a.device, c_grid is not None)
     _chkvec(bias, "bias", f32)
-    ws = split_weight(w, taps, cache=cache_w)      # (an activation in the W position - attention scores of the VAE - is not kept)
+    # the W operand is the pre-split bf16 planes of w (an activation in the W position - attention scores of the VAE - is not kept)
+    ws = split_weight(w, taps, cache=cache_w)
     g = _lib.GemmArgs()
     g.A, g.lda, g.W, g.bias, g.C, g.ldc = a.data_ptr(), a.stride(0), ws.data_ptr(), _p(bias), out.data_ptr(), out.stride(0)
     g.M, g.N, g.K, g.epilogue, g.act = M, N, K, epilogue, act
-    if a_grid is not None:
-        if stride2:
-            (a_grid.fill_stride2_sym if stride2 == "sym" else a_grid.fill_stride2)(g.a_map)
-        else:
-            a_grid.fill(g.a_map)
-        if conv3x3:
-            g.ntaps, g.k_per_tap = 9, a.shape[1]
-            for t, sh in enumerate(a_grid.tap_shifts_stride2() if stride2 else a_grid.tap_shifts()):
-                g.tap_shift[t] = sh
-        elif conv_taps is not None:
-            g.ntaps, g.k_per_tap = len(conv_taps), a.shape[1]
-            for t, sh in enumerate(conv_taps):
-                g.tap_shift[t] = sh
-    if c_grid is not None:
-        c_grid.fill(g.c_map)
-        for name, t in (("res", res), ("blend", blend)):
-            if t is not None and t.shape[0] != c_grid.rows:
-                raise RuntimeError(f"gemm: {name} must be a padded grid when c_grid is given")
-    if gate is not None:
-        _chk2d(gate, "gate", f32)
-        g.gate, g.ld_gate, g.rows_per_gate = gate.data_ptr(), gate.stride(0), rows_per_gate
-    if res is not None:
-        _chk2d(res, "res", f32)
-        g.res, g.ld_res, g.res_mod = res.data_ptr(), res.stride(0), res_mod
-    if blend is not None:
-        _chk2d(blend, "blend", f32)
-        _chkvec(alpha, "alpha", f32)
-        g.blend, g.ld_blend, g.alpha, g.rows_per_alpha = blend.data_ptr(), blend.stride(0), alpha.data_ptr(), rows_per_alpha
-    if rms_w is not None:
-        _chkvec(rms_w, "rms_w", f32)
-        g.rms_w, g.rms_ncols, g.rms_eps = rms_w.data_ptr(), rms_ncols, rms_eps
-    groups = (taps + 8) // 9                                  # one set of fp32 partial slices per group of 9 taps
+    _gemm_operands(g, f32, f32, gate, rows_per_gate, res, res_mod, blend, alpha, rows_per_alpha, rms_w, rms_ncols, rms_eps)
+    _gemm_maps(g, a, a_grid, conv3x3, stride2, conv_taps, c_grid, res, blend)
+    # scratch, grown on demand: the operand planes of A + one set of fp32 partial slices per group of 9 taps
+    a_rows = a_grid.rows if a_grid is not None else M
+    groups = (taps + 8) // 9
     need = 4 * a_rows * (K // taps) + 256 + 4 * M * N * groups
     tiles = ((M + 255) // 256) * ((N + 255) // 256)
     if tiles * groups <= 128:
         need += 4 * M * N * min(32, 256 // tiles)          # room for the kernel's own split-K rule
     wsb = _f32_workspace(a.device, need)
     g.workspace, g.workspace_bytes = wsb.data_ptr(), wsb.numel() * 4
-    _lib.check(_lib.load().dwm_gemm_f32(C.byref(g), _stream()), "dwm_gemm_f32")
+    _call("dwm_gemm_f32", C.byref(g))
     return out
 
 
-_F32_WORKSPACES: dict = {}
-
-
-def _f32_workspace(device: torch.device, nbytes: int) -> torch.Tensor:
-    """scratch of dwm_gemm_f32 (operand planes + fp32 partial sums), one per (device, stream), grown on demand"""
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-    ws = _F32_WORKSPACES.get(key)
-    if ws is None or ws.numel() * 4 < nbytes:
-        ws = _F32_WORKSPACES[key] = torch.empty((nbytes + (64 << 20)) // 4, dtype=torch.float32, device=device)
-    return ws
-
-
 _WORKSPACES: dict = {}
+_F32_WORKSPACES: dict = {}
 GEMM_WORKSPACE_BYTES = 1 << 30          # 1 GiB per (device, stream): up to ~8 K ranges of the largest weight gradient (12288 x 1536 fp32)
 
 
-def _gemm_workspace(device: torch.device) -> torch.Tensor:
-    """fp32 scratch of the split-K GEMM path, one per (device, stream): partial tiles live there only between the
-    two kernels of one dwm_gemm_bf16 call, so calls on one stream share it."""
+def _workspace(cache: dict, device: torch.device, nbytes: int, slack: int = 0) -> torch.Tensor:
+    """fp32 scratch of at least `nbytes`, one per (device, stream) in `cache`; a new one is allocated with `slack` bytes to spare"""
     key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-    ws = _WORKSPACES.get(key)
-    if ws is None:
-        ws = _WORKSPACES[key] = torch.empty(GEMM_WORKSPACE_BYTES // 4, dtype=torch.float32, device=device)
+    ws = cache.get(key)
+    if ws is None or ws.numel() * 4 < nbytes:
+        ws = cache[key] = torch.empty((nbytes + slack) // 4, dtype=f32, device=device)
     return ws
+
+
+def _f32_workspace(device: torch.device, nbytes: int) -> torch.Tensor:
+    """scratch of dwm_gemm_f32 (operand planes + fp32 partial sums), grown on demand to the need + 64 MiB"""
+    return _workspace(_F32_WORKSPACES, device, nbytes, 64 << 20)
+
+
+def _gemm_workspace(device: torch.device) -> torch.Tensor:
+    """fp32 scratch of the split-K GEMM path, a fixed size: partial tiles live there only between the
+    two kernels of one dwm_gemm_bf16 call, so calls on one stream share it."""
+    return _workspace(_WORKSPACES, device, GEMM_WORKSPACE_BYTES)
 
 
 # ---------------------------------------------------------------------------- attention
@@ -592,9 +570,38 @@ def rowmap_temporal_pointwise(B: int, T: int, V: int, h: int, w: int) -> RowMap:
                   ldiv=(BIG, BIG), lstride=(V * hw, 0, 0))
 
 
+def _attn_problem(a, q, heads, scale, rowmap):
+    """the part of a dwm_attn_args every form shares: heads (64 wide), the softmax scale and the row map"""
+    a.heads, a.head_dim = heads, 64
+    if q.shape[1] != heads * 64:
+        raise RuntimeError("attention: head_dim must be 64")
+    a.scale = float(scale) if scale is not None else 64 ** -0.5
+    for i in range(3):
+        a.pdiv[i], a.pmod[i], a.pstride[i] = rowmap.pdiv[i], rowmap.pmod[i], rowmap.pstride[i]
+        a.lstride[i] = rowmap.lstride[i]
+    a.ldiv[0], a.ldiv[1] = rowmap.ldiv
+
+
+def _attn_lse(a, lse):
+    """hand the optional log-sum-exp output to a filled dwm_attn_args"""
+    if lse is not None:
+        if lse.dtype != f32 or not lse.is_contiguous() or lse.numel() != a.n_problems * a.heads * (a.L0 + a.L1):
+            raise RuntimeError("lse: fp32 contiguous [n_problems, heads, L0+L1] expected")
+        a.lse = lse.data_ptr()
+
+
+def _attn_bwd_launch(b, lse):
+    """dwm_attention_bwd on a filled dwm_attn_bwd_args, with the forward's lse and a `delta` scratch of its size"""
+    b.fwd.lse = lse.data_ptr()
+    delta = torch.empty(lse.numel(), dtype=f32, device=lse.device)
+    b.delta = delta.data_ptr()
+    _call("dwm_attention_bwd", C.byref(b))
+    delta.record_stream(torch.cuda.current_stream())
+
+
 def _attn_args(a, q, k, v, out, rowmap, heads, q1, k1, v1, out1, scale, group_mask, dense_mask):
     """fill a dwm_attn_args; returns the uint8 mask tensor that must outlive the launch (or None)"""
-    dt = q.dtype if q.dtype == torch.float32 else bf16             # fp32: the accuracy path (dwm_attention_f32)
+    dt = _dt(q)                                                    # fp32: the accuracy path (dwm_attention_f32)
     for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
         _chk2d(t, name, dt)
     if not (q.stride(0) == k.stride(0) == v.stride(0)):
@@ -610,14 +617,7 @@ def _attn_args(a, q, k, v, out, rowmap, heads, q1, k1, v1, out1, scale, group_ma
         a.q1, a.k1, a.v1, a.ld1 = q1.data_ptr(), k1.data_ptr(), v1.data_ptr(), q1.stride(0)
         a.o1, a.ldo1 = out1.data_ptr(), out1.stride(0)
         a.L1 = q1.shape[0] // rowmap.n_problems
-    a.heads, a.head_dim = heads, 64
-    if q.shape[1] != heads * 64:
-        raise RuntimeError("attention: head_dim must be 64")
-    a.scale = float(scale) if scale is not None else 64 ** -0.5
-    for i in range(3):
-        a.pdiv[i], a.pmod[i], a.pstride[i] = rowmap.pdiv[i], rowmap.pmod[i], rowmap.pstride[i]
-        a.lstride[i] = rowmap.lstride[i]
-    a.ldiv[0], a.ldiv[1] = rowmap.ldiv
+    _attn_problem(a, q, heads, scale, rowmap)
     a.mask_mode = 0
     keep = None
     if group_mask is not None:
@@ -646,14 +646,8 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tens
     a = _lib.AttnArgs()
     keep = _attn_args(a, q, k, v, out, rowmap, heads, q1, k1, v1, out1, scale, group_mask, dense_mask)
     a.variant = variant | _ATTN_ENV_VARIANT
-    if lse is not None:
-        if lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() != a.n_problems * heads * (a.L0 + a.L1):
-            raise RuntimeError("lse: fp32 contiguous [n_problems, heads, L0+L1] expected")
-        a.lse = lse.data_ptr()
-    if q.dtype == torch.float32:
-        _lib.check(_lib.load().dwm_attention_f32(C.byref(a), _stream()), "dwm_attention_f32")
-    else:
-        _lib.check(_lib.load().dwm_attention_fwd(C.byref(a), _stream()), "dwm_attention_fwd")
+    _attn_lse(a, lse)
+    _call("dwm_attention_f32" if q.dtype == f32 else "dwm_attention_fwd", C.byref(a))
     if keep is not None:
         keep.record_stream(torch.cuda.current_stream())
 
@@ -665,7 +659,6 @@ def attention_bwd(q, k, v, out, dout, dq, dk, dv, rowmap: RowMap, heads: int, ls
     writes dq/dk/dv (and dq1/dk1/dv1), which share a row stride per segment."""
     b = _lib.AttnBwdArgs()
     keep = _attn_args(b.fwd, q, k, v, out, rowmap, heads, q1, k1, v1, out1, scale, group_mask, dense_mask)
-    b.fwd.lse = lse.data_ptr()
     for name, t in (("dout", dout), ("dq", dq), ("dk", dk), ("dv", dv)):
         _chk2d(t, name)
     if dout.stride(0) != out.stride(0) or not (dq.stride(0) == dk.stride(0) == dv.stride(0)):
@@ -677,17 +670,15 @@ def attention_bwd(q, k, v, out, dout, dq, dk, dv, rowmap: RowMap, heads: int, ls
         if dout1.stride(0) != out1.stride(0):
             raise RuntimeError("dout1 must be laid out like out1")
         b.do1, b.dq1, b.dk1, b.dv1, b.ld_d1 = dout1.data_ptr(), dq1.data_ptr(), dk1.data_ptr(), dv1.data_ptr(), dq1.stride(0)
-    delta = torch.empty(lse.numel(), dtype=torch.float32, device=lse.device)
-    b.delta = delta.data_ptr()
-    _lib.check(_lib.load().dwm_attention_bwd(C.byref(b), _stream()), "dwm_attention_bwd")
-    delta.record_stream(torch.cuda.current_stream())
+    _attn_bwd_launch(b, lse)
     if keep is not None:
         keep.record_stream(torch.cuda.current_stream())
 
 
 def _cross_args(a, q, k, v, out, n_problems, heads, scale):
+    """fill a dwm_attn_args in `cross` mode: queries = segment 0, keys / values = segment 1, each addressed from one base"""
     for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
-        _chk2d(t, name, q.dtype if q.dtype == torch.float32 else bf16)
+        _chk2d(t, name, _dt(q))
     if k.stride(0) != v.stride(0) or q.shape[0] % n_problems or k.shape[0] % n_problems:
         raise RuntimeError("cross_attention: k, v must share a row stride; rows must be n_problems * L")
     a.q0 = a.q1 = q.data_ptr()
@@ -696,15 +687,7 @@ def _cross_args(a, q, k, v, out, n_problems, heads, scale):
     a.ld0, a.ld1 = q.stride(0), k.stride(0)
     a.o0, a.ldo0 = out.data_ptr(), out.stride(0)
     a.L0, a.L1, a.n_problems = q.shape[0] // n_problems, k.shape[0] // n_problems, n_problems
-    a.heads, a.head_dim = heads, 64
-    if q.shape[1] != heads * 64:
-        raise RuntimeError("attention: head_dim must be 64")
-    a.scale = float(scale) if scale is not None else 64 ** -0.5
-    rm = rowmap_identity(n_problems, a.L0)
-    for i in range(3):
-        a.pdiv[i], a.pmod[i], a.pstride[i] = rm.pdiv[i], rm.pmod[i], rm.pstride[i]
-        a.lstride[i] = rm.lstride[i]
-    a.ldiv[0], a.ldiv[1] = rm.ldiv
+    _attn_problem(a, q, heads, scale, rowmap_identity(n_problems, a.L0))
     a.cross = 1
 
 
@@ -716,16 +699,10 @@ def cross_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torc
     lse (optional, fp32 [n_problems, heads, Lq + Lk], the query entries are written): for cross_attention_bwd."""
     a = _lib.AttnArgs()
     _cross_args(a, q, k, v, out, n_problems, heads, scale)
-    if lse is not None:
-        if lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() != n_problems * heads * (a.L0 + a.L1):
-            raise RuntimeError("lse: fp32 contiguous [n_problems, heads, Lq+Lk] expected")
-        a.lse = lse.data_ptr()
-    if q.dtype == torch.float32:                 # the fp32 accuracy path (UNet text cross-attention)
-        if lse is not None:
-            raise NotImplementedError("cross_attention: no LSE output on the fp32 path (inference only)")
-        _lib.check(_lib.load().dwm_attention_f32(C.byref(a), _stream()), "dwm_attention_f32")
-        return
-    _lib.check(_lib.load().dwm_attention_fwd(C.byref(a), _stream()), "dwm_attention_fwd")
+    _attn_lse(a, lse)
+    if q.dtype == f32 and lse is not None:       # the fp32 accuracy path (UNet text cross-attention)
+        raise NotImplementedError("cross_attention: no LSE output on the fp32 path (inference only)")
+    _call("dwm_attention_f32" if q.dtype == f32 else "dwm_attention_fwd", C.byref(a))
 
 
 def cross_attention_bwd(q, k, v, out, dout, dq, dk, dv, n_problems: int, heads: int, lse: torch.Tensor,
@@ -733,7 +710,6 @@ def cross_attention_bwd(q, k, v, out, dout, dq, dk, dv, n_problems: int, heads: 
     """Backward of `cross_attention`: dq like q (row stride of its own), dk / dv like k / v (sharing a row stride)."""
     b = _lib.AttnBwdArgs()
     _cross_args(b.fwd, q, k, v, out, n_problems, heads, scale)
-    b.fwd.lse = lse.data_ptr()
     for name, t in (("dout", dout), ("dq", dq), ("dk", dk), ("dv", dv)):
         _chk2d(t, name)
     if dout.stride(0) != out.stride(0) or dk.stride(0) != dv.stride(0) or dq.shape != q.shape or dk.shape != k.shape:
@@ -744,13 +720,14 @@ def cross_attention_bwd(q, k, v, out, dout, dq, dk, dv, n_problems: int, heads: 
     b.dk0 = b.dk1 = dk.data_ptr()
     b.dv0 = b.dv1 = dv.data_ptr()
     b.ld_d0, b.ld_d1 = dq.stride(0), dk.stride(0)
-    delta = torch.empty(lse.numel(), dtype=torch.float32, device=lse.device)
-    b.delta = delta.data_ptr()
-    _lib.check(_lib.load().dwm_attention_bwd(C.byref(b), _stream()), "dwm_attention_bwd")
-    delta.record_stream(torch.cuda.current_stream())
+    _attn_bwd_launch(b, lse)
 
 
 # -------------------------------------------------------------------------------- norms
+# entry point -> dtype of (x, xsum, everything else: out / out2, weight / bias, the modulation matrices, addvec)
+_LAYERNORM_FORMS = {"dwm_layernorm": (bf16, bf16, bf16), "dwm_layernorm_f32": (f32, f32, f32), "dwm_layernorm_x32": (f32, f32, bf16)}
+
+
 def layernorm(x: torch.Tensor, *, eps: float, out: Optional[torch.Tensor] = None,
               weight: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
               scale: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None,
@@ -761,12 +738,10 @@ def layernorm(x: torch.Tensor, *, eps: float, out: Optional[torch.Tensor] = None
               xsum: Optional[torch.Tensor] = None, x32: bool = False):
     """See dwm_layernorm.  scale/shift (and scale2/shift2) are 2-D views sharing one row
     stride (column slices of the AdaLN modulation matrix).  x32: x (and xsum) are the fp32 residual stream of the bf16
-    forward, everything else bf16 (dwm_layernorm_x32)."""
-    if x32:
-        return _layernorm_x32(x, eps=eps, out=out, weight=weight, bias=bias, scale=scale, shift=shift, rows_per_mod=rows_per_mod,
-                              scale2=scale2, shift2=shift2, out2=out2, addvec=addvec, rows_per_add=rows_per_add, xsum=xsum)
-    dt = x.dtype if x.dtype == torch.float32 else bf16             # fp32: the accuracy path (dwm_layernorm_f32)
-    _chk2d(x, "x", dt)
+    forward, everything else bf16 (dwm_layernorm_x32); otherwise fp32 x: the accuracy path (dwm_layernorm_f32)."""
+    fn = "dwm_layernorm_x32" if x32 else "dwm_layernorm_f32" if x.dtype == f32 else "dwm_layernorm"
+    xdt, sumdt, dt = _LAYERNORM_FORMS[fn]
+    _chk2d(x, "x", xdt)
     rows, D = x.shape
     if out is None:
         out = torch.empty((rows, D), dtype=dt, device=x.device)
@@ -794,47 +769,9 @@ def layernorm(x: torch.Tensor, *, eps: float, out: Optional[torch.Tensor] = None
         _chk2d(addvec, "addvec", dt)
         a.addvec, a.ld_add, a.rows_per_add = addvec.data_ptr(), addvec.stride(0), rows_per_add
         if xsum is not None:
-            _chk2d(xsum, "xsum", dt)
+            _chk2d(xsum, "xsum", sumdt)
             a.xsum, a.ldxsum = xsum.data_ptr(), xsum.stride(0)
-    if dt == torch.float32:
-        _lib.check(_lib.load().dwm_layernorm_f32(C.byref(a), _stream()), "dwm_layernorm_f32")
-        return out
-    _lib.check(_lib.load().dwm_layernorm(C.byref(a), _stream()), "dwm_layernorm")
-    return out
-
-
-def _layernorm_x32(x, *, eps, out, weight, bias, scale, shift, rows_per_mod, scale2, shift2, out2, addvec, rows_per_add, xsum):
-    _chk2d(x, "x", torch.float32)
-    rows, D = x.shape
-    if out is None:
-        out = torch.empty((rows, D), dtype=bf16, device=x.device)
-    _chk2d(out, "out")
-    a = _lib.LayerNormArgs()
-    a.x, a.ldx, a.y, a.ldy = x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0)
-    a.rows, a.D, a.eps = rows, D, eps
-    _chkvec(weight, "weight")
-    _chkvec(bias, "bias")
-    a.weight, a.bias = _p(weight), _p(bias)
-    if scale is not None:
-        _chk2d(scale, "scale")
-        _chk2d(shift, "shift")
-        if scale.stride(0) != shift.stride(0):
-            raise RuntimeError("scale/shift must share a row stride")
-        a.scale, a.shift, a.ld_mod, a.rows_per_mod = scale.data_ptr(), shift.data_ptr(), scale.stride(0), rows_per_mod
-    if out2 is not None:
-        _chk2d(out2, "out2")
-        _chk2d(scale2, "scale2")
-        _chk2d(shift2, "shift2")
-        if scale2.stride(0) != a.ld_mod or shift2.stride(0) != a.ld_mod:
-            raise RuntimeError("scale2/shift2 must share the row stride of scale/shift")
-        a.y2, a.ldy2, a.scale2, a.shift2 = out2.data_ptr(), out2.stride(0), scale2.data_ptr(), shift2.data_ptr()
-    if addvec is not None:
-        _chk2d(addvec, "addvec")
-        a.addvec, a.ld_add, a.rows_per_add = addvec.data_ptr(), addvec.stride(0), rows_per_add
-        if xsum is not None:
-            _chk2d(xsum, "xsum", torch.float32)
-            a.xsum, a.ldxsum = xsum.data_ptr(), xsum.stride(0)
-    _lib.check(_lib.load().dwm_layernorm_x32(C.byref(a), _stream()), "dwm_layernorm_x32")
+    _call(fn, C.byref(a))
     return out
 
 
@@ -842,137 +779,106 @@ def rmsnorm_heads_(x: torch.Tensor, w_expanded: torch.Tensor, eps: float) -> tor
     """In-place per-64-wide-head RMSNorm of x[rows, ncols]; w_expanded [ncols]."""
     _chk2d(x, "x")
     _chkvec(w_expanded, "w")
-    _lib.check(_lib.load().dwm_rmsnorm_heads(x.data_ptr(), x.stride(0), x.shape[0], x.shape[1],
-                                             w_expanded.data_ptr(), eps, _stream()), "dwm_rmsnorm_heads")
+    _call("dwm_rmsnorm_heads", x.data_ptr(), x.stride(0), x.shape[0], x.shape[1], w_expanded.data_ptr(), eps)
     return x
 
 
 # -------------------------------------------------------------------------- elementwise
 def silu(x: torch.Tensor) -> torch.Tensor:
-    if x.dtype == torch.float32:
-        _chkvec(x, "x", torch.float32)
-        y = torch.empty_like(x)
-        _lib.check(_lib.load().dwm_silu_f32(x.data_ptr(), y.data_ptr(), x.numel(), _stream()), "dwm_silu_f32")
-        return y
-    _chkvec(x, "x")
+    _chkvec(x, "x", _dt(x))
     y = torch.empty_like(x)
-    _lib.check(_lib.load().dwm_silu(x.data_ptr(), y.data_ptr(), x.numel(), _stream()), "dwm_silu")
+    _call("dwm_silu_f32" if x.dtype == f32 else "dwm_silu", x.data_ptr(), y.data_ptr(), x.numel())
     return y
 
 
 def timestep_sinusoid(t: torch.Tensor, channels: int, dtype: torch.dtype = bf16) -> torch.Tensor:
     """diffusers Timesteps(channels, flip_sin_to_cos=True, downscale_freq_shift=0) -> [n, channels] bf16 (or fp32: the accuracy path)."""
-    t = t.reshape(-1).to(torch.float32).contiguous()
+    t = t.reshape(-1).to(f32).contiguous()
     if not t.is_cuda:
         raise RuntimeError("timestep_sinusoid: expected a device tensor")
-    if dtype == torch.float32:
-        out = torch.empty((t.numel(), channels), dtype=torch.float32, device=t.device)
-        _lib.check(_lib.load().dwm_timestep_sinusoid_f32(t.data_ptr(), t.numel(), channels, out.data_ptr(), _stream()),
-                   "dwm_timestep_sinusoid_f32")
-        return out
-    out = torch.empty((t.numel(), channels), dtype=bf16, device=t.device)
-    _lib.check(_lib.load().dwm_timestep_sinusoid(t.data_ptr(), t.numel(), channels, out.data_ptr(), _stream()),
-               "dwm_timestep_sinusoid")
+    out = torch.empty((t.numel(), channels), dtype=f32 if dtype == f32 else bf16, device=t.device)
+    _call("dwm_timestep_sinusoid_f32" if dtype == f32 else "dwm_timestep_sinusoid", t.data_ptr(), t.numel(), channels, out.data_ptr())
     return out
+
+
+def _image_token_rows(what: str, x: torch.Tensor, p: int, ldo: Optional[int], dtype: torch.dtype):
+    """patchify / unshuffle_tokens: check the [I, C, H, W] image, allocate the [I*(H/p)*(W/p), ldo] token rows -> (out, ldo)"""
+    if not x.is_cuda or x.dim() != 4 or not x.is_contiguous() or x.dtype not in (f32, bf16):
+        raise RuntimeError(f"{what}: expected a contiguous fp32/bf16 [I,C,H,W] device tensor")
+    I, Cc, H, W = x.shape
+    ldo = ldo or (Cc * p * p + 63) // 64 * 64
+    if dtype == f32 and x.dtype != f32:
+        raise RuntimeError(f"{what}: the fp32 form takes fp32 images")
+    return torch.empty((I * (H // p) * (W // p), ldo), dtype=f32 if dtype == f32 else bf16, device=x.device), ldo
 
 
 def patchify(x: torch.Tensor, p: int, ldo: Optional[int] = None, dtype: torch.dtype = bf16) -> torch.Tensor:
     """[I, C, H, W] (fp32 / bf16) -> [I*(H/p)*(W/p), ldo] im2col rows (zero padded to ldo), bf16 (or fp32: the accuracy path)."""
-    if not x.is_cuda or x.dim() != 4 or not x.is_contiguous() or x.dtype not in (torch.float32, bf16):
-        raise RuntimeError("patchify: expected a contiguous fp32/bf16 [I,C,H,W] device tensor")
-    I, Cc, H, W = x.shape
-    cols = Cc * p * p
-    ldo = ldo or (cols + 63) // 64 * 64
-    if dtype == torch.float32:
-        if x.dtype != torch.float32:
-            raise RuntimeError("patchify: the fp32 path takes fp32 images")
-        out = torch.empty((I * (H // p) * (W // p), ldo), dtype=torch.float32, device=x.device)
-        _lib.check(_lib.load().dwm_patchify_f32(x.data_ptr(), I, Cc, H, W, p, out.data_ptr(), ldo, _stream()), "dwm_patchify_f32")
-        return out
-    out = torch.empty((I * (H // p) * (W // p), ldo), dtype=bf16, device=x.device)
-    _lib.check(_lib.load().dwm_patchify(x.data_ptr(), int(x.dtype == torch.float32), I, Cc, H, W, p,
-                                        out.data_ptr(), ldo, _stream()), "dwm_patchify")
+    out, ldo = _image_token_rows("patchify", x, p, ldo, dtype)
+    if dtype == f32:
+        _call("dwm_patchify_f32", x.data_ptr(), *x.shape, p, out.data_ptr(), ldo)
+    else:                                   # the bf16 entry point takes either image dtype, as a flag
+        _call("dwm_patchify", x.data_ptr(), int(x.dtype == f32), *x.shape, p, out.data_ptr(), ldo)
     return out
 
 
 def unpatchify(x: torch.Tensor, I: int, Cc: int, h: int, w: int, p: int) -> torch.Tensor:
-    if x.dtype == torch.float32:
-        _chk2d(x, "x", torch.float32)
-        out = torch.empty((I, Cc, h * p, w * p), dtype=torch.float32, device=x.device)
-        _lib.check(_lib.load().dwm_unpatchify_f32(x.data_ptr(), x.stride(0), I, Cc, h, w, p, out.data_ptr(), _stream()),
-                   "dwm_unpatchify_f32")
-        return out
-    _chk2d(x, "x")
-    out = torch.empty((I, Cc, h * p, w * p), dtype=bf16, device=x.device)
-    _lib.check(_lib.load().dwm_unpatchify(x.data_ptr(), x.stride(0), I, Cc, h, w, p, out.data_ptr(), _stream()),
-               "dwm_unpatchify")
+    dt = _dt(x)
+    _chk2d(x, "x", dt)
+    out = torch.empty((I, Cc, h * p, w * p), dtype=dt, device=x.device)
+    _call("dwm_unpatchify_f32" if dt == f32 else "dwm_unpatchify", x.data_ptr(), x.stride(0), I, Cc, h, w, p, out.data_ptr())
     return out
 
 
 def cfg_euler_step(pred: torch.Tensor, latents: torch.Tensor, guidance: float, dsigma,
                    model_in: Optional[torch.Tensor] = None, group_elems: int = 0) -> None:
     """latents(fp32, in place) += dsigma * (u + g (c - u)) with pred = [uncond; cond] bf16 (fp32 pred + fp32 model_in: the
-    accuracy path)."""
+    accuracy path).  dsigma: a number, or per-frame steps [n / group_elems] fp32 (diffusion forcing)."""
     n = latents.numel()
-    if pred.dtype == torch.float32:
-        if pred.numel() != 2 * n or not pred.is_contiguous() or not pred.is_cuda or latents.dtype != torch.float32 or not latents.is_contiguous():
-            raise RuntimeError("cfg_euler_step: fp32 pred must be contiguous with 2x the (fp32, contiguous) latent elements")
-        if model_in is not None and (model_in.dtype != torch.float32 or model_in.numel() != 2 * n or not model_in.is_contiguous()):
-            raise RuntimeError("cfg_euler_step: model_in of the fp32 path must be contiguous fp32 [2, n]")
-        grp = dsigma if torch.is_tensor(dsigma) else None
-        if grp is not None and (grp.dtype != torch.float32 or not grp.is_cuda or not grp.is_contiguous() or grp.numel() * group_elems != n):
-            raise RuntimeError("cfg_euler_step: dsigma must be a contiguous fp32 device tensor with n / group_elems entries")
-        _lib.check(_lib.load().dwm_cfg_euler_step_f32(pred.data_ptr(), latents.data_ptr(), _p(model_in), n, float(guidance),
-                                                      0.0 if grp is not None else float(dsigma), _p(grp), group_elems, _stream()),
-                   "dwm_cfg_euler_step_f32")
-        return
-    if pred.dtype != bf16 or pred.numel() != 2 * n or not pred.is_contiguous() or not pred.is_cuda:
-        raise RuntimeError("cfg_euler_step: pred must be contiguous bf16 with 2x the latent elements")
-    if latents.dtype != torch.float32 or not latents.is_contiguous() or not latents.is_cuda:
+    dt = _dt(pred)
+    if pred.dtype != dt or pred.numel() != 2 * n or not pred.is_contiguous() or not pred.is_cuda:
+        raise RuntimeError("cfg_euler_step: pred must be contiguous bf16 (fp32: the accuracy path) with 2x the latent elements")
+    # known asymmetry, kept as it was: the fp32 form never checked that latents is a device tensor
+    if latents.dtype != f32 or not latents.is_contiguous() or (dt == bf16 and not latents.is_cuda):
         raise RuntimeError("cfg_euler_step: latents must be contiguous fp32")
-    if model_in is not None and (model_in.dtype != bf16 or model_in.numel() != 2 * n or not model_in.is_contiguous()):
-        raise RuntimeError("cfg_euler_step: model_in must be contiguous bf16 [2, n]")
-    if torch.is_tensor(dsigma):          # per-frame steps [n / group_elems] fp32 (diffusion forcing)
-        if dsigma.dtype != torch.float32 or not dsigma.is_cuda or not dsigma.is_contiguous() or dsigma.numel() * group_elems != n:
-            raise RuntimeError("cfg_euler_step: dsigma must be a contiguous fp32 device tensor with n / group_elems entries")
-        _lib.check(_lib.load().dwm_cfg_euler_step_grouped(pred.data_ptr(), latents.data_ptr(), _p(model_in), n, float(guidance),
-                                                          dsigma.data_ptr(), group_elems, _stream()), "dwm_cfg_euler_step_grouped")
-        return
-    _lib.check(_lib.load().dwm_cfg_euler_step(pred.data_ptr(), latents.data_ptr(), _p(model_in), n,
-                                              float(guidance), float(dsigma), _stream()), "dwm_cfg_euler_step")
+    if model_in is not None and (model_in.dtype != dt or model_in.numel() != 2 * n or not model_in.is_contiguous()):
+        raise RuntimeError("cfg_euler_step: model_in must be contiguous [2, n] of pred's dtype")
+    grouped = torch.is_tensor(dsigma)
+    if grouped and (dsigma.dtype != f32 or not dsigma.is_cuda or not dsigma.is_contiguous() or dsigma.numel() * group_elems != n):
+        raise RuntimeError("cfg_euler_step: dsigma must be a contiguous fp32 device tensor with n / group_elems entries")
+    head = (pred.data_ptr(), latents.data_ptr(), _p(model_in), n, float(guidance))
+    if dt == f32:                           # one entry point for both kinds of step: the scalar, then the (nullable) table
+        _call("dwm_cfg_euler_step_f32", *head, 0.0 if grouped else float(dsigma), dsigma.data_ptr() if grouped else None, group_elems)
+    elif grouped:
+        _call("dwm_cfg_euler_step_grouped", *head, dsigma.data_ptr(), group_elems)
+    else:
+        _call("dwm_cfg_euler_step", *head, float(dsigma))
 
 
 def cfg_multistep(pred: torch.Tensor, latents: torch.Tensor, x0_prev: torch.Tensor, guidance: float, kx: float, ko: float,
                   A: float, B: float, Cc: float, model_in: Optional[torch.Tensor] = None) -> None:
     """CFG combine + linear multistep scheduler update (see dwm_cfg_multistep); latents / x0_prev fp32 in place."""
     n = latents.numel()
-    if pred.dtype not in (bf16, torch.float32) or pred.numel() != 2 * n or not pred.is_contiguous() or not pred.is_cuda:
+    if pred.dtype not in (bf16, f32) or pred.numel() != 2 * n or not pred.is_contiguous() or not pred.is_cuda:
         raise RuntimeError("cfg_multistep: pred must be contiguous bf16 (fp32: the accuracy path) with 2x the latent elements")
     for t in (latents, x0_prev):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+        if t.dtype != f32 or not t.is_contiguous() or t.numel() != n:
             raise RuntimeError("cfg_multistep: latents / x0_prev must be contiguous fp32 of the same size")
     if model_in is not None and (model_in.dtype != pred.dtype or model_in.numel() != 2 * n or not model_in.is_contiguous()):
         raise RuntimeError("cfg_multistep: model_in must be contiguous, of pred's dtype and size")
-    if pred.dtype == torch.float32:
-        _lib.check(_lib.load().dwm_cfg_multistep_f32(pred.data_ptr(), latents.data_ptr(), x0_prev.data_ptr(), _p(model_in), n,
-                                                     float(guidance), float(kx), float(ko), float(A), float(B), float(Cc), _stream()),
-                   "dwm_cfg_multistep_f32")
-        return
-    _lib.check(_lib.load().dwm_cfg_multistep(pred.data_ptr(), latents.data_ptr(), x0_prev.data_ptr(), _p(model_in), n,
-                                             float(guidance), float(kx), float(ko), float(A), float(B), float(Cc), _stream()),
-               "dwm_cfg_multistep")
+    _call("dwm_cfg_multistep_f32" if pred.dtype == f32 else "dwm_cfg_multistep", pred.data_ptr(), latents.data_ptr(),
+          x0_prev.data_ptr(), _p(model_in), n, float(guidance), float(kx), float(ko), float(A), float(B), float(Cc))
 
 
 def ray_features(cam: torch.Tensor, h: int, w: int, ldo: int = 128, dtype: torch.dtype = bf16) -> torch.Tensor:
     """cam fp32 [I, 21] (see dwm_ray_features) -> bf16 (or, the fp32 accuracy path, fp32) [I*h*w, ldo]: RayEncoder's 72
     positional-encoding inputs per token."""
-    if cam.dtype != torch.float32 or cam.dim() != 2 or cam.shape[1] != 21 or not cam.is_contiguous() or not cam.is_cuda:
+    if cam.dtype != f32 or cam.dim() != 2 or cam.shape[1] != 21 or not cam.is_contiguous() or not cam.is_cuda:
         raise RuntimeError("ray_features: cam must be a contiguous fp32 device tensor [I, 21]")
-    if dtype not in (bf16, torch.float32):
+    if dtype not in (bf16, f32):
         raise RuntimeError("ray_features: bf16 or fp32 output")
     out = torch.empty((cam.shape[0] * h * w, ldo), dtype=dtype, device=cam.device)
-    fn = "dwm_ray_features_f32" if dtype == torch.float32 else "dwm_ray_features"
-    _lib.check(getattr(_lib.load(), fn)(cam.data_ptr(), cam.shape[0], h, w, out.data_ptr(), ldo, _stream()), fn)
+    _call("dwm_ray_features_f32" if dtype == f32 else "dwm_ray_features", cam.data_ptr(), cam.shape[0], h, w, out.data_ptr(), ldo)
     return out
 
 
@@ -981,14 +887,13 @@ def frame_affine(x: torch.Tensor, y: torch.Tensor, coef: torch.Tensor, group_ele
     """out = coef[g, 0] * x + coef[g, 1] * y (fp32), g = element // group_elems; see dwm_frame_affine."""
     n = x.numel()
     for t in (x, y):
-        if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or t.numel() != n:
+        if t.dtype != f32 or not t.is_contiguous() or not t.is_cuda or t.numel() != n:
             raise RuntimeError("frame_affine: x / y must be contiguous fp32 device tensors of one size")
-    if coef.dtype != torch.float32 or not coef.is_contiguous() or not coef.is_cuda or coef.numel() * group_elems != 2 * n:
+    if coef.dtype != f32 or not coef.is_contiguous() or not coef.is_cuda or coef.numel() * group_elems != 2 * n:
         raise RuntimeError("frame_affine: coef must be a contiguous fp32 device tensor [n / group_elems, 2]")
     if out is None and out_bf16 is None:
         out = torch.empty_like(x)
-    _lib.check(_lib.load().dwm_frame_affine(x.data_ptr(), y.data_ptr(), coef.data_ptr(), _p(out), _p(out_bf16), n, group_elems,
-                                            _stream()), "dwm_frame_affine")
+    _call("dwm_frame_affine", x.data_ptr(), y.data_ptr(), coef.data_ptr(), _p(out), _p(out_bf16), n, group_elems)
     return out if out is not None else out_bf16
 
 
@@ -1000,69 +905,67 @@ def cfg_ddim_step(pred: torch.Tensor, latents: torch.Tensor, coef: torch.Tensor,
     guidance None: pred holds n elements; otherwise pred = [uncond; cond] with 2n."""
     n = latents.numel()
     cfg = guidance is not None
-    if pred.dtype not in (bf16, torch.float32) or pred.numel() != (2 * n if cfg else n) or not pred.is_contiguous() or not pred.is_cuda:
+    if pred.dtype not in (bf16, f32) or pred.numel() != (2 * n if cfg else n) or not pred.is_contiguous() or not pred.is_cuda:
         raise RuntimeError("cfg_ddim_step: pred must be a contiguous bf16 / fp32 device tensor with n (2n with guidance) elements")
     for t in (latents, noise, x0_out):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n or not t.is_cuda):
+        if t is not None and (t.dtype != f32 or not t.is_contiguous() or t.numel() != n or not t.is_cuda):
             raise RuntimeError("cfg_ddim_step: latents / noise / x0_out must be contiguous fp32 device tensors of one size")
-    if coef.dtype != torch.float32 or not coef.is_contiguous() or not coef.is_cuda or coef.numel() * group_elems != 6 * n:
+    if coef.dtype != f32 or not coef.is_contiguous() or not coef.is_cuda or coef.numel() * group_elems != 6 * n:
         raise RuntimeError("cfg_ddim_step: coef must be a contiguous fp32 device tensor [n / group_elems, 6]")
     if model_in is not None and (model_in.dtype != bf16 or model_in.numel() != (2 * n if cfg else n) or not model_in.is_contiguous()):
         raise RuntimeError("cfg_ddim_step: model_in must be contiguous bf16")
-    _lib.check(_lib.load().dwm_cfg_ddim_step(pred.data_ptr(), int(pred.dtype == torch.float32), int(cfg), latents.data_ptr(), _p(model_in),
-                                             _p(x0_out), _p(noise), coef.data_ptr(), n, group_elems, float(guidance or 0.0),
-                                             int(prediction_type), float(clip_range), int(bool(use_clipped_model_output)), _stream()),
-               "dwm_cfg_ddim_step")
+    _call("dwm_cfg_ddim_step", pred.data_ptr(), int(pred.dtype == f32), int(cfg), latents.data_ptr(), _p(model_in), _p(x0_out),
+          _p(noise), coef.data_ptr(), n, group_elems, float(guidance or 0.0), int(prediction_type), float(clip_range),
+          int(bool(use_clipped_model_output)))
 
 
 def unshuffle_tokens(x: torch.Tensor, r: int, ldo: Optional[int] = None, dtype: torch.dtype = bf16) -> torch.Tensor:
     """PixelUnshuffle(r): [I, C, H, W] (fp32 / bf16) -> token-major [I*(H/r)*(W/r), ldo], bf16 or (dtype=torch.float32, fp32
     input: the accuracy path) fp32; columns past C r r are zero."""
-    if not x.is_cuda or x.dim() != 4 or not x.is_contiguous() or x.dtype not in (torch.float32, bf16):
-        raise RuntimeError("unshuffle_tokens: expected a contiguous fp32/bf16 [I,C,H,W] device tensor")
-    I, Cc, H, W = x.shape
-    cols = Cc * r * r
-    ldo = ldo or (cols + 63) // 64 * 64
-    if dtype == torch.float32:
-        if x.dtype != torch.float32:
-            raise RuntimeError("unshuffle_tokens: the fp32 form takes fp32 images")
-        out = torch.empty((I * (H // r) * (W // r), ldo), dtype=torch.float32, device=x.device)
-        _lib.check(_lib.load().dwm_unshuffle_tokens_f32(x.data_ptr(), I, Cc, H, W, r, out.data_ptr(), ldo, _stream()), "dwm_unshuffle_tokens_f32")
-        return out
-    out = torch.empty((I * (H // r) * (W // r), ldo), dtype=bf16, device=x.device)
-    _lib.check(_lib.load().dwm_unshuffle_tokens(x.data_ptr(), int(x.dtype == torch.float32), I, Cc, H, W, r,
-                                                out.data_ptr(), ldo, _stream()), "dwm_unshuffle_tokens")
+    out, ldo = _image_token_rows("unshuffle_tokens", x, r, ldo, dtype)
+    if dtype == f32:
+        _call("dwm_unshuffle_tokens_f32", x.data_ptr(), *x.shape, r, out.data_ptr(), ldo)
+    else:                                   # the bf16 entry point takes either image dtype, as a flag
+        _call("dwm_unshuffle_tokens", x.data_ptr(), int(x.dtype == f32), *x.shape, r, out.data_ptr(), ldo)
     return out
 
 
 def avgpool2_tokens(x: torch.Tensor, I: int, h: int, w: int) -> torch.Tensor:
     """AvgPool2d(2) on token-major [I*h*w, C] -> [I*(h/2)*(w/2), C]."""
-    dt = torch.float32 if x.dtype == torch.float32 else bf16
+    dt = _dt(x)
     _chk2d(x, "x", dt)
     if not x.is_contiguous() or x.shape[0] != I * h * w:
         raise RuntimeError("avgpool2_tokens: x must be contiguous [I*h*w, C]")
     out = torch.empty((I * (h // 2) * (w // 2), x.shape[1]), dtype=dt, device=x.device)
-    fn = _lib.load().dwm_avgpool2_tokens_f32 if dt == torch.float32 else _lib.load().dwm_avgpool2_tokens
-    _lib.check(fn(x.data_ptr(), I, h, w, x.shape[1], out.data_ptr(), _stream()), "dwm_avgpool2_tokens")
+    _call("dwm_avgpool2_tokens_f32" if dt == f32 else "dwm_avgpool2_tokens", x.data_ptr(), I, h, w, x.shape[1], out.data_ptr())
     return out
 
 
 def add_(y: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     """y += x (contiguous device tensors of one shape).  y bf16: x bf16, or fp32 (the fp32 sum is rounded once).  y fp32 (the
     fp32 residual stream): x fp32 or bf16."""
-    if y.shape != x.shape or y.dtype not in (bf16, torch.float32) or x.dtype not in (bf16, torch.float32) \
+    if y.shape != x.shape or y.dtype not in (bf16, f32) or x.dtype not in (bf16, f32) \
             or not y.is_contiguous() or not x.is_contiguous() or not y.is_cuda:
         raise RuntimeError("add_: expected contiguous device tensors of one shape (bf16 / fp32)")
-    if y.dtype == torch.float32:
-        if x.dtype == torch.float32:
-            _lib.check(_lib.load().dwm_add_f32_f32_inplace(y.data_ptr(), x.data_ptr(), y.numel(), _stream()), "dwm_add_f32_f32_inplace")
-        else:
-            cast_f32(x, out=y, accumulate=True)
-    elif x.dtype == torch.float32:
-        _lib.check(_lib.load().dwm_add_f32_inplace(y.data_ptr(), x.data_ptr(), y.numel(), _stream()), "dwm_add_f32_inplace")
+    if y.dtype == f32 and x.dtype == bf16:
+        cast_f32(x, out=y, accumulate=True)
+    elif y.dtype == f32:
+        _call("dwm_add_f32_f32_inplace", y.data_ptr(), x.data_ptr(), y.numel())
     else:
-        _lib.check(_lib.load().dwm_add_inplace(y.data_ptr(), x.data_ptr(), y.numel(), _stream()), "dwm_add_inplace")
+        _call("dwm_add_f32_inplace" if x.dtype == f32 else "dwm_add_inplace", y.data_ptr(), x.data_ptr(), y.numel())
     return y
+
+
+def _gn_maps(grid, img_map: Optional[tuple]):
+    """the (dwm_rowmap2d, dwm_gn_imgmap) pair of the group-norm entry points, forward and backward: the padded grid of the
+    normalised-side matrix (or none) and the image / pixel -> token row map (iv, pn, s_ihi, s_ilo, s_phi) (or none)"""
+    m = _lib.RowMap2D()
+    if grid is not None:
+        grid.fill(m)
+    im = _lib.GnImgMap()
+    if img_map is not None:
+        im.iv, im.pn, im.s_ihi, im.s_ilo, im.s_phi = img_map
+    return m, im
 
 
 def groupnorm_silu(x: torch.Tensor, I: int, P: int, gamma: torch.Tensor, beta: torch.Tensor, groups: int,
@@ -1072,7 +975,7 @@ def groupnorm_silu(x: torch.Tensor, I: int, P: int, gamma: torch.Tensor, beta: t
     interior of a padded grid `out` [out_grid.rows, C] whose border must already be zero.  img_map =
     (iv, pn, s_ihi, s_ilo, s_phi): image i / pixel p -> token row (see dwm_groupnorm_silu_mapped).
     zmap = dict(mod [z rows, 2C], frames, videos, h, w, shift, zt): CogVideoXSpatialNorm3D (dwm_groupnorm_spatial)."""
-    dt = torch.float32 if x.dtype == torch.float32 else bf16           # fp32: the accuracy path (dwm_groupnorm_silu_f32)
+    dt = _dt(x)                                                        # fp32: the accuracy path (dwm_groupnorm_silu_f32)
     _chk2d(x, "x", dt)
     if not x.is_contiguous() or x.shape[0] != I * P:
         raise RuntimeError("groupnorm_silu: x must be contiguous [I*P, C]")
@@ -1084,36 +987,24 @@ def groupnorm_silu(x: torch.Tensor, I: int, P: int, gamma: torch.Tensor, beta: t
         out = (torch.zeros if out_grid is not None else torch.empty)((rows, Cc), dtype=dt, device=x.device)
     if out.shape != (rows, Cc) or not out.is_contiguous() or out.dtype != dt:
         raise RuntimeError("groupnorm_silu: bad out")
-    stats = torch.empty(_lib.load().dwm_groupnorm_stats_floats(I, P, groups), dtype=torch.float32, device=x.device)
-    m = _lib.RowMap2D()
-    if out_grid is not None:
-        out_grid.fill(m)
-    im = _lib.GnImgMap()
-    if img_map is not None:
-        im.iv, im.pn, im.s_ihi, im.s_ilo, im.s_phi = img_map
-    if dt == torch.float32 and zmap is None:
-        _lib.check(_lib.load().dwm_groupnorm_silu_f32(x.data_ptr(), out.data_ptr(), I, P, Cc, groups, eps, gamma.data_ptr(),
-                                                      beta.data_ptr(), int(silu), stats.data_ptr(), C.byref(m), C.byref(im),
-                                                      _stream()), "dwm_groupnorm_silu_f32")
+    stats = torch.empty(_lib.load().dwm_groupnorm_stats_floats(I, P, groups), dtype=f32, device=x.device)
+    m, im = _gn_maps(out_grid, img_map)
+    head = (x.data_ptr(), out.data_ptr(), I, P, Cc, groups, eps, gamma.data_ptr(), beta.data_ptr(), int(silu), stats.data_ptr(),
+            C.byref(m), C.byref(im))
+    if zmap is None:
+        _call("dwm_groupnorm_silu_f32" if dt == f32 else "dwm_groupnorm_silu_mapped", *head)
         return out
-    if zmap is not None:
-        mod = zmap["mod"]
-        _chk2d(mod, "zmap.mod", dt)
-        zm = _lib.GnZMap()
-        zm.mod, zm.ld_mod = mod.data_ptr(), mod.stride(0)
-        zm.frames, zm.videos, zm.h, zm.w, zm.shift = zmap["frames"], zmap["videos"], zmap["h"], zmap["w"], zmap["shift"]
-        for t, z in enumerate(zmap["zt"]):
-            zm.zt[t] = z
-        need = ((max(zmap["zt"]) + 1) * zmap["videos"]) * (zmap["h"] >> zmap["shift"]) * (zmap["w"] >> zmap["shift"])
-        if mod.shape[0] < need or mod.shape[1] < 2 * Cc:
-            raise RuntimeError("groupnorm_silu: zmap.mod is smaller than the latent grid it is indexed with")
-        fn = "dwm_groupnorm_spatial_f32" if dt == torch.float32 else "dwm_groupnorm_spatial"
-        _lib.check(getattr(_lib.load(), fn)(x.data_ptr(), out.data_ptr(), I, P, Cc, groups, eps, gamma.data_ptr(), beta.data_ptr(),
-                                            int(silu), stats.data_ptr(), C.byref(m), C.byref(im), C.byref(zm), _stream()), fn)
-        return out
-    _lib.check(_lib.load().dwm_groupnorm_silu_mapped(x.data_ptr(), out.data_ptr(), I, P, Cc, groups, eps, gamma.data_ptr(),
-                                                     beta.data_ptr(), int(silu), stats.data_ptr(), C.byref(m), C.byref(im),
-                                                     _stream()), "dwm_groupnorm_silu_mapped")
+    mod = zmap["mod"]
+    _chk2d(mod, "zmap.mod", dt)
+    zm = _lib.GnZMap()
+    zm.mod, zm.ld_mod = mod.data_ptr(), mod.stride(0)
+    zm.frames, zm.videos, zm.h, zm.w, zm.shift = zmap["frames"], zmap["videos"], zmap["h"], zmap["w"], zmap["shift"]
+    for t, z in enumerate(zmap["zt"]):
+        zm.zt[t] = z
+    need = ((max(zmap["zt"]) + 1) * zmap["videos"]) * (zmap["h"] >> zmap["shift"]) * (zmap["w"] >> zmap["shift"])
+    if mod.shape[0] < need or mod.shape[1] < 2 * Cc:
+        raise RuntimeError("groupnorm_silu: zmap.mod is smaller than the latent grid it is indexed with")
+    _call("dwm_groupnorm_spatial_f32" if dt == f32 else "dwm_groupnorm_spatial", *head, C.byref(zm))
     return out
 
 
@@ -1122,7 +1013,7 @@ def frame_mix(x: torch.Tensor, frame_elems: int, f0, f1, w0, w1, out: Optional[t
     flat tensor x (temporal average pooling / temporal nearest upsampling of the CogVideoX VAE)."""
     n = len(f0)
     dt = x.dtype
-    if dt not in (bf16, torch.float32) or not x.is_cuda or not x.is_contiguous() or x.numel() % frame_elems != 0:
+    if dt not in (bf16, f32) or not x.is_cuda or not x.is_contiguous() or x.numel() % frame_elems != 0:
         raise RuntimeError("frame_mix: x must be a contiguous bf16 (or, the fp32 accuracy path, fp32) device tensor of whole frames")
     nin = x.numel() // frame_elems
     if not (len(f1) == len(w0) == len(w1) == n) or n == 0 or n > 64 or max(max(f0), max(f1)) >= nin:
@@ -1135,14 +1026,13 @@ def frame_mix(x: torch.Tensor, frame_elems: int, f0, f1, w0, w1, out: Optional[t
     fm.n_out = n
     for j in range(n):
         fm.f0[j], fm.f1[j], fm.w0[j], fm.w1[j] = f0[j], f1[j], w0[j], w1[j]
-    fn = "dwm_frame_mix_f32" if dt == torch.float32 else "dwm_frame_mix_bf16"
-    _lib.check(getattr(_lib.load(), fn)(x.data_ptr(), out.data_ptr(), frame_elems, C.byref(fm), _stream()), fn)
+    _call("dwm_frame_mix_f32" if dt == f32 else "dwm_frame_mix_bf16", x.data_ptr(), out.data_ptr(), frame_elems, C.byref(fm))
     return out
 
 
 def upsample2_padded(x: torch.Tensor, I: int, h: int, w: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """nearest 2x upsample of token-major [I*h*w, C] into the padded grid of the [I, 2h, 2w] image."""
-    dt = torch.float32 if x.dtype == torch.float32 else bf16
+    dt = _dt(x)
     _chk2d(x, "x", dt)
     if not x.is_contiguous() or x.shape[0] != I * h * w:
         raise RuntimeError("upsample2_padded: x must be contiguous [I*h*w, C]")
@@ -1150,14 +1040,13 @@ def upsample2_padded(x: torch.Tensor, I: int, h: int, w: int, out: Optional[torc
     if out is None:
         out = torch.zeros((g.rows, x.shape[1]), dtype=dt, device=x.device)
     _chk2d(out, "out", dt)
-    fn = _lib.load().dwm_upsample2_padded_f32 if dt == torch.float32 else _lib.load().dwm_upsample2_padded
-    _lib.check(fn(x.data_ptr(), out.data_ptr(), I, h, w, x.shape[1], _stream()), "dwm_upsample2_padded")
+    _call("dwm_upsample2_padded_f32" if dt == f32 else "dwm_upsample2_padded", x.data_ptr(), out.data_ptr(), I, h, w, x.shape[1])
     return out
 
 
 def pad_tokens(x: torch.Tensor, grid: PaddedGrid, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """compact token rows [grid.pixels, C] -> interior of a zero-bordered padded grid [grid.rows, C]."""
-    dt = torch.float32 if x.dtype == torch.float32 else bf16
+    dt = _dt(x)
     _chk2d(x, "x", dt)
     if not x.is_contiguous() or x.shape[0] != grid.pixels:
         raise RuntimeError("pad_tokens: x must be contiguous [grid.pixels, C]")
@@ -1166,48 +1055,46 @@ def pad_tokens(x: torch.Tensor, grid: PaddedGrid, out: Optional[torch.Tensor] = 
     _chk2d(out, "out", dt)
     m = _lib.RowMap2D()
     grid.fill(m)
-    fn = _lib.load().dwm_pad_tokens_f32 if dt == torch.float32 else _lib.load().dwm_pad_tokens
-    _lib.check(fn(x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1], C.byref(m), _stream()), "dwm_pad_tokens")
+    _call("dwm_pad_tokens_f32" if dt == f32 else "dwm_pad_tokens", x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1], C.byref(m))
     return out
 
 
 def softmax_rows(x: torch.Tensor, scale: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    dt = torch.float32 if x.dtype == torch.float32 else bf16
+    dt = _dt(x)
     _chk2d(x, "x", dt)
     out = torch.empty_like(x) if out is None else out
     _chk2d(out, "out", dt)
-    fn = _lib.load().dwm_softmax_rows_f32 if dt == torch.float32 else _lib.load().dwm_softmax_rows
-    _lib.check(fn(x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1], x.stride(0), float(scale), _stream()), "dwm_softmax_rows")
+    _call("dwm_softmax_rows_f32" if dt == f32 else "dwm_softmax_rows", x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1], x.stride(0),
+          float(scale))
     return out
 
 
 def cast_bf16(x: torch.Tensor) -> torch.Tensor:
     if x.dtype == bf16:
         return x
-    if x.dtype != torch.float32 or not x.is_cuda:
+    if x.dtype != f32 or not x.is_cuda:
         raise RuntimeError("cast_bf16: expected an fp32 device tensor")
     x = x.contiguous()
     out = torch.empty(x.shape, dtype=bf16, device=x.device)
-    _lib.check(_lib.load().dwm_cast_f32_to_bf16(x.data_ptr(), out.data_ptr(), x.numel(), _stream()),
-               "dwm_cast_f32_to_bf16")
+    _call("dwm_cast_f32_to_bf16", x.data_ptr(), out.data_ptr(), x.numel())
     return out
 
 
 def cast_f32(x: torch.Tensor, out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
-    """fp32 (+)= bf16, 2-D row-strided or contiguous (dwm_cast_bf16_to_f32): the entry of the fp32 residual stream"""
+    """fp32 (+)= bf16, 2-D row-strided or contiguous (dwm_cast_bf16_to_f32): the entry of the fp32 residual stream, and the
+    fp32 gradient accumulation of training (train_ops.cast_f32 is this function)"""
     if x.dtype != bf16 or not x.is_cuda:
         raise RuntimeError("cast_f32: expected a bf16 device tensor")
     x2 = x if x.dim() == 2 else x.reshape(1, -1)
     _chk2d(x2, "x")
     if out is None:
-        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        out = torch.empty(x.shape, dtype=f32, device=x.device)
         accumulate = False
     o2 = out if out.dim() == 2 else out.reshape(1, -1)
-    _chk2d(o2, "out", torch.float32)
+    _chk2d(o2, "out", f32)
     if o2.shape != x2.shape:
         raise RuntimeError("cast_f32: shape mismatch")
-    _lib.check(_lib.load().dwm_cast_bf16_to_f32(x2.data_ptr(), x2.stride(0), o2.data_ptr(), o2.stride(0), x2.shape[0], x2.shape[1],
-                                                int(accumulate), _stream()), "dwm_cast_bf16_to_f32")
+    _call("dwm_cast_bf16_to_f32", x2.data_ptr(), x2.stride(0), o2.data_ptr(), o2.stride(0), x2.shape[0], x2.shape[1], int(accumulate))
     return out
 
 
@@ -1215,5 +1102,5 @@ def tr_probe(offsets: torch.Tensor) -> torch.Tensor:
     """Diagnostic: semantics probe of ds_read_b64_tr_b16 (tests only)."""
     offsets = offsets.to(torch.int32).contiguous()
     out = torch.empty((64, 4), dtype=torch.int16, device=offsets.device)
-    _lib.check(_lib.load().dwm_debug_tr_probe(offsets.data_ptr(), out.data_ptr(), _stream()), "dwm_debug_tr_probe")
+    _call("dwm_debug_tr_probe", offsets.data_ptr(), out.data_ptr())
     return out

@@ -10,87 +10,79 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import _lib, ops
-from .ops import _p, _stream, ACT_GELU_TANH, ACT_SILU  # noqa: F401
+from .ops import _call, _chk2d, _p, cast_f32, ACT_GELU_TANH, ACT_SILU  # noqa: F401  (cast_f32: fp32 (+)= bf16, used as train_ops.cast_f32)
 
 bf16 = torch.bfloat16
 # weight gradients by dwm_gemm_tn (operands as they are); "0": the transposes + NT GEMM path (A/B measurements)
 WGRAD_TN = os.environ.get("DWM_WGRAD_TN", "1") != "0"
 
 
-def _rows2d(t: torch.Tensor, name: str, dtype=bf16) -> None:
-    if t.dtype != dtype or t.dim() != 2 or t.stride(1) != 1 or not t.is_cuda:
-        raise RuntimeError(f"{name}: expected a {dtype} CUDA matrix with unit column stride, got {t.dtype} {tuple(t.shape)} {t.stride()}")
-
-
 def transpose(x: torch.Tensor, rows_pad: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x [rows, cols] -> out [cols, rows_pad] (zero-filled beyond `rows`; default: rows rounded up to 64)."""
-    _rows2d(x, "x")
+    _chk2d(x, "x")
     rows, cols = x.shape
     if rows_pad is None:
         rows_pad = (rows + 63) // 64 * 64
     if out is None:
         out = torch.empty((cols, rows_pad), dtype=bf16, device=x.device)
-    _lib.check(_lib.load().dwm_transpose_bf16(_p(x), x.stride(0), rows, cols, _p(out), out.stride(0), rows_pad, _stream()),
-               "dwm_transpose_bf16")
+    _call("dwm_transpose_bf16", _p(x), x.stride(0), rows, cols, _p(out), out.stride(0), rows_pad)
     return out
 
 
 def segsum(a: torch.Tensor, b: Optional[torch.Tensor] = None, rows_per_group: Optional[int] = None,
            out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fp32 [groups, ncols]: per-group column sums of a (* b); `out` (if given) is accumulated into."""
-    _rows2d(a, "a")
+    _chk2d(a, "a")
     rows, ncols = a.shape
     rpg = rows if rows_per_group is None else rows_per_group
     groups = (rows + rpg - 1) // rpg
     if out is None:
         out = torch.zeros((groups, ncols), dtype=torch.float32, device=a.device)
     if b is not None:
-        _rows2d(b, "b")
-    _lib.check(_lib.load().dwm_segsum(_p(a), a.stride(0), _p(b), 0 if b is None else b.stride(0), rows, ncols, rpg,
-                                      _p(out), out.stride(0), _stream()), "dwm_segsum")
+        _chk2d(b, "b")
+    _call("dwm_segsum", _p(a), a.stride(0), _p(b), 0 if b is None else b.stride(0), rows, ncols, rpg, _p(out), out.stride(0))
     return out
 
 
 def segsum_diff(a: torch.Tensor, b: torch.Tensor, b2: torch.Tensor, rows_per_group: Optional[int] = None) -> torch.Tensor:
     """fp32 [groups, ncols]: per-group column sums of a * (b - b2), the difference taken in fp32 before the product."""
     for t, n in ((a, "a"), (b, "b"), (b2, "b2")):
-        _rows2d(t, n)
+        _chk2d(t, n)
     if b.shape != a.shape or b2.shape != a.shape:
         raise RuntimeError("segsum_diff: shape mismatch")
     rows, ncols = a.shape
     rpg = rows if rows_per_group is None else rows_per_group
     out = torch.zeros(((rows + rpg - 1) // rpg, ncols), dtype=torch.float32, device=a.device)
-    _lib.check(_lib.load().dwm_segsum_diff(_p(a), a.stride(0), _p(b), b.stride(0), _p(b2), b2.stride(0), rows, ncols, rpg,
-                                           _p(out), out.stride(0), _stream()), "dwm_segsum_diff")
+    _call("dwm_segsum_diff", _p(a), a.stride(0), _p(b), b.stride(0), _p(b2), b2.stride(0), rows, ncols, rpg,
+          _p(out), out.stride(0))
     return out
 
 
 def act_fwd(x: torch.Tensor, act: int) -> torch.Tensor:
     y = torch.empty_like(x)
-    _lib.check(_lib.load().dwm_act_fwd(_p(x), _p(y), x.numel(), act, _stream()), "dwm_act_fwd")
+    _call("dwm_act_fwd", _p(x), _p(y), x.numel(), act)
     return y
 
 
 def act_bwd(x: torch.Tensor, dy: torch.Tensor, act: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     dx = torch.empty_like(x) if out is None else out
-    _lib.check(_lib.load().dwm_act_bwd(_p(x), _p(dy), _p(dx), x.numel(), act, _stream()), "dwm_act_bwd")
+    _call("dwm_act_bwd", _p(x), _p(dy), _p(dx), x.numel(), act)
     return dx
 
 
 def geglu_fwd(u: torch.Tensor) -> torch.Tensor:
-    _rows2d(u, "u")
+    _chk2d(u, "u")
     rows, two = u.shape
     g = torch.empty((rows, two // 2), dtype=bf16, device=u.device)
-    _lib.check(_lib.load().dwm_geglu_fwd(_p(u), u.stride(0), rows, two // 2, _p(g), g.stride(0), _stream()), "dwm_geglu_fwd")
+    _call("dwm_geglu_fwd", _p(u), u.stride(0), rows, two // 2, _p(g), g.stride(0))
     return g
 
 
 def geglu_bwd(u: torch.Tensor, dg: torch.Tensor) -> torch.Tensor:
-    _rows2d(u, "u"); _rows2d(dg, "dg")
+    _chk2d(u, "u"); _chk2d(dg, "dg")
     rows, two = u.shape
     du = torch.empty_like(u)
-    _lib.check(_lib.load().dwm_geglu_bwd(_p(u), u.stride(0), _p(dg), dg.stride(0), rows, two // 2, _p(du), du.stride(0),
-                                         _stream()), "dwm_geglu_bwd")
+    _call("dwm_geglu_bwd", _p(u), u.stride(0), _p(dg), dg.stride(0), rows, two // 2, _p(du), du.stride(0))
     return du
 
 
@@ -99,23 +91,23 @@ def rowcombine(a: torch.Tensor, *, gate_a: Optional[torch.Tensor] = None, rows_p
                b: Optional[torch.Tensor] = None, coef_b: Optional[torch.Tensor] = None, rows_per_coef_b: int = 1,
                out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = a * gate_a[row // rpg] * coef_a[row // rpc] + b * coef_b[row // rpc] (see dwm_rowcombine)."""
-    _rows2d(a, "a")
+    _chk2d(a, "a")
     if out is None:
         out = torch.empty((a.shape[0], a.shape[1]), dtype=bf16, device=a.device)
     r = _lib.RowCombineArgs()
     r.a, r.lda = _p(a), a.stride(0)
     if gate_a is not None:
-        _rows2d(gate_a, "gate_a")
+        _chk2d(gate_a, "gate_a")
         r.gate_a, r.ld_gate_a, r.rows_per_gate_a = _p(gate_a), gate_a.stride(0), rows_per_gate_a
     if coef_a is not None:
         r.coef_a, r.rows_per_coef_a = _p(coef_a), rows_per_coef_a
     if b is not None:
-        _rows2d(b, "b")
+        _chk2d(b, "b")
         r.b, r.ldb = _p(b), b.stride(0)
         if coef_b is not None:
             r.coef_b, r.rows_per_coef_b = _p(coef_b), rows_per_coef_b
     r.out, r.ldo, r.rows, r.ncols = _p(out), out.stride(0), a.shape[0], a.shape[1]
-    _lib.check(_lib.load().dwm_rowcombine(C.byref(r), _stream()), "dwm_rowcombine")
+    _call("dwm_rowcombine", C.byref(r))
     return out
 
 
@@ -127,7 +119,7 @@ def layernorm_bwd(x: torch.Tensor, dy: torch.Tensor, *, eps: float, dx: Optional
                   dgamma2: Optional[torch.Tensor] = None, dbeta2: Optional[torch.Tensor] = None,
                   grad_per_group: bool = False) -> torch.Tensor:
     """Backward of ops.layernorm; dgamma/dbeta[/2] are fp32 [G or 1, D] accumulators (see dwm_layernorm_bwd)."""
-    _rows2d(x, "x"); _rows2d(dy, "dy")
+    _chk2d(x, "x"); _chk2d(dy, "dy")
     rows, D = x.shape
     if dx is None:
         dx = torch.empty((rows, D), dtype=bf16, device=x.device)
@@ -149,27 +141,25 @@ def layernorm_bwd(x: torch.Tensor, dy: torch.Tensor, *, eps: float, dx: Optional
     if g0 is not None:
         a.dgamma, a.dbeta, a.dgamma2, a.dbeta2 = _p(dgamma), _p(dbeta), _p(dgamma2), _p(dbeta2)
         a.ld_grad, a.grad_per_group = g0.stride(0), int(grad_per_group)
-    _lib.check(_lib.load().dwm_layernorm_bwd(C.byref(a), _stream()), "dwm_layernorm_bwd")
+    _call("dwm_layernorm_bwd", C.byref(a))
     return dx
 
 
 def rmsnorm_heads_train_(x: torch.Tensor, w_expanded: torch.Tensor, eps: float) -> torch.Tensor:
     """In-place per-head RMSNorm of x [rows, ncols]; returns rinv fp32 [rows, ncols // 64]."""
-    _rows2d(x, "x")
+    _chk2d(x, "x")
     rows, ncols = x.shape
     rinv = torch.empty((rows, ncols // 64), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().dwm_rmsnorm_heads_train(_p(x), x.stride(0), rows, ncols, _p(w_expanded), eps, _p(rinv), _stream()),
-               "dwm_rmsnorm_heads_train")
+    _call("dwm_rmsnorm_heads_train", _p(x), x.stride(0), rows, ncols, _p(w_expanded), eps, _p(rinv))
     return rinv
 
 
 def rmsnorm_heads_bwd_(y: torch.Tensor, rinv: torch.Tensor, w_expanded: torch.Tensor, dy: torch.Tensor,
                        dw: torch.Tensor) -> torch.Tensor:
     """dy -> dx in place; dw fp32 [ncols] accumulated."""
-    _rows2d(y, "y"); _rows2d(dy, "dy")
+    _chk2d(y, "y"); _chk2d(dy, "dy")
     rows, ncols = y.shape
-    _lib.check(_lib.load().dwm_rmsnorm_heads_bwd(_p(y), y.stride(0), _p(rinv), _p(w_expanded), _p(dy), dy.stride(0), rows, ncols,
-                                                 _p(dw), _stream()), "dwm_rmsnorm_heads_bwd")
+    _call("dwm_rmsnorm_heads_bwd", _p(y), y.stride(0), _p(rinv), _p(w_expanded), _p(dy), dy.stride(0), rows, ncols, _p(dw))
     return dy
 
 
@@ -178,8 +168,8 @@ def adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, p
     for t in (p, g, m, v):
         if t.dtype != torch.float32 or not t.is_contiguous():
             raise RuntimeError("adamw_: fp32 contiguous tensors expected")
-    _lib.check(_lib.load().dwm_adamw(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), p.numel(), lr, beta1, beta2, eps, weight_decay,
-                                     1.0 - beta1 ** step, 1.0 - beta2 ** step, grad_scale, _stream()), "dwm_adamw")
+    _call("dwm_adamw", _p(p), _p(g), _p(m), _p(v), _p(p_bf16), p.numel(), lr, beta1, beta2, eps, weight_decay,
+          1.0 - beta1 ** step, 1.0 - beta2 ** step, grad_scale)
 
 
 ADAMW_CHUNK = 1 << 16            # elements per workgroup of the multi-tensor AdamW
@@ -210,22 +200,8 @@ def adamw_multi_(ps, gs, ms, vs, shadows, *, lr: float, beta1: float, beta2: flo
             bs.append(torch.arange(nb, dtype=torch.int64) * ADAMW_CHUNK)
         _ADAMW_BLOCKS.clear()                                                           # one parameter list at a time
         tab = _ADAMW_BLOCKS[key] = (torch.cat(bi).to(dev), torch.cat(bs).to(dev))
-    _lib.check(_lib.load().dwm_adamw_multi(_p(items), _p(tab[0]), _p(tab[1]), tab[0].numel(), ADAMW_CHUNK, lr, beta1, beta2, eps,
-                                           weight_decay, 1.0 - beta1 ** step, 1.0 - beta2 ** step, grad_scale, _stream()),
-               "dwm_adamw_multi")
-
-
-def cast_f32(x: torch.Tensor, out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
-    """fp32 (+)= bf16 matrix / vector."""
-    x2 = x if x.dim() == 2 else x.reshape(1, -1)
-    _rows2d(x2, "x")
-    if out is None:
-        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-        accumulate = False
-    o2 = out if out.dim() == 2 else out.reshape(1, -1)
-    _lib.check(_lib.load().dwm_cast_bf16_to_f32(_p(x2), x2.stride(0), _p(o2), o2.stride(0), x2.shape[0], x2.shape[1],
-                                                int(accumulate), _stream()), "dwm_cast_bf16_to_f32")
-    return out
+    _call("dwm_adamw_multi", _p(items), _p(tab[0]), _p(tab[1]), tab[0].numel(), ADAMW_CHUNK, lr, beta1, beta2, eps,
+          weight_decay, 1.0 - beta1 ** step, 1.0 - beta2 ** step, grad_scale)
 
 
 # ------------------------------------------------------------------------------------------ composites
@@ -241,8 +217,8 @@ def gemm_tn(dy: torch.Tensor, x: torch.Tensor, tap_shifts: Optional[Sequence[int
     gradient of a linear layer (no taps) or - dy and x on the same padded token grid, dy zero on its border rows - of a
     convolution with those taps, from the row-major operands as they are (no transposes, no per-tap gathers).
     dy [M, N], M % 64 == 0; x [rows, C]."""
-    _rows2d(dy, "dy")
-    _rows2d(x, "x")
+    _chk2d(dy, "dy")
+    _chk2d(x, "x")
     M, N = dy.shape
     Cc = x.shape[1]
     ntaps = len(tap_shifts) if tap_shifts is not None else 0
@@ -253,7 +229,7 @@ def gemm_tn(dy: torch.Tensor, x: torch.Tensor, tap_shifts: Optional[Sequence[int
     cols = max(ntaps, 1) * Cc
     if out is None:
         out = torch.empty((N, cols), dtype=bf16, device=dy.device)
-    _rows2d(out, "out")
+    _chk2d(out, "out")
     if out.shape != (N, cols):
         raise RuntimeError(f"gemm_tn: out must be [{N}, {cols}]")
     ws = ops._gemm_workspace(dy.device)
@@ -264,7 +240,7 @@ def gemm_tn(dy: torch.Tensor, x: torch.Tensor, tap_shifts: Optional[Sequence[int
     for t in range(ntaps):
         g.tap_shift[t] = int(tap_shifts[t])
     g.workspace, g.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-    _lib.check(_lib.load().dwm_gemm_tn(C.byref(g), _stream()), "dwm_gemm_tn")
+    _call("dwm_gemm_tn", C.byref(g))
     return out
 
 
@@ -311,8 +287,8 @@ def groupnorm_bwd(x: torch.Tensor, dz: torch.Tensor, I: int, P: int, gamma: torc
     """Backward of ops.groupnorm_silu: x [I*P, C] = the forward input, dz = gradient of the forward output - compact
     rows, or (dz_grid) the padded grid the forward wrote into; returns dx [I*P, C] bf16 (accumulate: added to the given dx);
     dgamma / dbeta: fp32 [C] accumulators (see dwm_groupnorm_bwd)."""
-    _rows2d(x, "x")
-    _rows2d(dz, "dz")
+    _chk2d(x, "x")
+    _chk2d(dz, "dz")
     Cc = x.shape[1]
     rows = dz_grid.rows if dz_grid is not None else I * P
     if not x.is_contiguous() or x.shape[0] != I * P or not dz.is_contiguous() or dz.shape != (rows, Cc):
@@ -324,17 +300,11 @@ def groupnorm_bwd(x: torch.Tensor, dz: torch.Tensor, I: int, P: int, gamma: torc
         if accumulate:
             raise RuntimeError("groupnorm_bwd: accumulate needs dx")
         dx = torch.empty_like(x)
-    _rows2d(dx, "dx")
+    _chk2d(dx, "dx")
     if dx.shape != x.shape or not dx.is_contiguous():
         raise RuntimeError("groupnorm_bwd: bad dx")
-    lib = _lib.load()
-    stats = torch.empty(2 * lib.dwm_groupnorm_stats_floats(I, P, groups), dtype=torch.float32, device=x.device)
-    m = _lib.RowMap2D()
-    if dz_grid is not None:
-        dz_grid.fill(m)
-    im = _lib.GnImgMap()
-    if img_map is not None:
-        im.iv, im.pn, im.s_ihi, im.s_ilo, im.s_phi = img_map
-    _lib.check(lib.dwm_groupnorm_bwd(_p(x), _p(dz), _p(dx), I, P, Cc, groups, eps, _p(gamma), _p(beta), int(silu), int(accumulate),
-                                     _p(stats), _p(dgamma), _p(dbeta), C.byref(m), C.byref(im), _stream()), "dwm_groupnorm_bwd")
+    stats = torch.empty(2 * _lib.load().dwm_groupnorm_stats_floats(I, P, groups), dtype=torch.float32, device=x.device)
+    m, im = ops._gn_maps(dz_grid, img_map)
+    _call("dwm_groupnorm_bwd", _p(x), _p(dz), _p(dx), I, P, Cc, groups, eps, _p(gamma), _p(beta), int(silu), int(accumulate),
+          _p(stats), _p(dgamma), _p(dbeta), C.byref(m), C.byref(im))
     return dx

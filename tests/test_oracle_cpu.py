@@ -1,6 +1,7 @@
 """CPU leg (`-m "not gpu"`): the oracle against its golden fixtures and internal
 cross-checks, the host-side logic (row maps, weight packing, schedule, FLOP model) and the
 C-ABI surface.  No kernel is executed here."""
+import ast
 import ctypes
 import os
 import re
@@ -385,7 +386,10 @@ def test_ctypes_structs_match_header_field_order():
     from opendwm_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "dwm_hip.h")).read()
     for cname, cls in (("dwm_gemm_args", _lib.GemmArgs), ("dwm_attn_args", _lib.AttnArgs),
-                       ("dwm_layernorm_args", _lib.LayerNormArgs), ("dwm_gemm_tn_args", _lib.GemmTnArgs)):
+                       ("dwm_layernorm_args", _lib.LayerNormArgs), ("dwm_gemm_tn_args", _lib.GemmTnArgs),
+                       ("dwm_rowmap2d", _lib.RowMap2D), ("dwm_attn_bwd_args", _lib.AttnBwdArgs), ("dwm_gn_imgmap", _lib.GnImgMap),
+                       ("dwm_gn_zmap", _lib.GnZMap), ("dwm_frame_mix", _lib.FrameMix), ("dwm_rowcombine_args", _lib.RowCombineArgs),
+                       ("dwm_layernorm_bwd_args", _lib.LayerNormBwdArgs), ("dwm_block_permute_args", _lib.BlockPermuteArgs)):
         body = hdr[hdr.index(f"typedef struct {cname}"):hdr.index(f"}} {cname};")]
         body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
         pos = -1
@@ -393,6 +397,46 @@ def test_ctypes_structs_match_header_field_order():
             m = re.search(rf"[\s\*,]{fname}\s*(\[\d+\])?\s*[,;]", body[pos + 1:])
             assert m, (cname, fname)
             pos = pos + 1 + m.start()
+
+
+def _entry_point_names(node, assigned):
+    """the entry-point names an expression handed to ops._call can stand for: a string literal, `a if c else b`, `a + b`, or a
+    local name every assignment of which is one of these; anything else is an error (the wrappers keep it that simple)"""
+    if isinstance(node, ast.Constant) and isinstance(node.value, str):
+        return {node.value}
+    if isinstance(node, ast.IfExp):
+        return _entry_point_names(node.body, assigned) | _entry_point_names(node.orelse, assigned)
+    if isinstance(node, ast.BinOp) and isinstance(node.op, ast.Add):
+        return {a + b for a in _entry_point_names(node.left, assigned) for b in _entry_point_names(node.right, assigned)}
+    if isinstance(node, ast.Name) and assigned.get(node.id):
+        return set().union(*(_entry_point_names(v, assigned) for v in assigned[node.id]))
+    raise AssertionError(f"line {node.lineno}: the entry point of this _call is not a literal (or a choice / sum of literals)")
+
+
+def test_wrappers_name_only_declared_entry_points():
+    """ops.py / train_ops.py look every entry point up by name (ops._call): each name - both where the dtype picks one - must be
+    declared in _lib.SIGNATURES, so that a misspelt one fails here and not at the first launch.  Reads the sources only."""
+    from opendwm_amd import _lib
+    seen = set()
+    for mod in ("ops.py", "train_ops.py"):
+        src = open(os.path.join(ROOT, "opendwm_amd", mod)).read()
+        assert src.count("_lib.check(") == (mod == "ops.py"), f"{mod}: only ops._call itself checks a return code"
+        for fn in ast.walk(ast.parse(src)):
+            if not isinstance(fn, ast.FunctionDef):
+                continue
+            assigned = {}
+            for n in ast.walk(fn):
+                if isinstance(n, ast.Assign) and len(n.targets) == 1 and isinstance(n.targets[0], ast.Name):
+                    assigned.setdefault(n.targets[0].id, []).append(n.value)
+            for n in ast.walk(fn):
+                if isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id == "_call":
+                    names = _entry_point_names(n.args[0], assigned)
+                    assert names <= set(_lib.SIGNATURES), (mod, fn.name, sorted(names - set(_lib.SIGNATURES)))
+                    seen |= names
+    # every paired form is seen through its wrapper's choice, e.g. all three LayerNorm entry points and both softmaxes
+    assert {"dwm_layernorm", "dwm_layernorm_f32", "dwm_layernorm_x32", "dwm_softmax_rows", "dwm_softmax_rows_f32",
+            "dwm_gemm_bf16", "dwm_gemm_f32", "dwm_gemm_tn", "dwm_groupnorm_bwd"} <= seen
+    assert len(seen) >= 60, sorted(seen)
 
 
 def test_entry_points_validate_their_arguments_before_touching_the_device():
