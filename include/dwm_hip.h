@@ -108,11 +108,10 @@ typedef struct dwm_gemm_args {
     dwm_rowmap2d c_map;                                         /* C, res and blend rows                     */
     int32_t ntaps; int32_t k_per_tap;
     int64_t tap_shift[27];                                      /* in rows; up to 3x3x3 taps (causal Conv3d) */
-    /* split-K (PLAIN / RESID epilogues): when the tile grid fills less than half of the GPU and K is long, the K
-     * axis is cut into ranges (one workgroup each), fp32 partial tiles go to `workspace` and a second kernel reduces
-     * them in a fixed order and applies the epilogue.  workspace: 16-byte aligned device scratch of workspace_bytes
-     * (>= 2 * M * N * 4 to be usable), owned by the caller, one per stream; NULL = never split.
-     * split_k: 0 = automatic, 1 = never, > 1 = exactly this many ranges (DWM_EUNSUPPORTED if impossible). */
+    /* split-K (PLAIN / RESID epilogues): the K axis is cut into ranges (one workgroup each), fp32 partial tiles go to `workspace`
+     * and a second kernel reduces them in a fixed order and applies the epilogue.  workspace: 16-byte aligned device scratch of
+     * workspace_bytes (>= 2 * M * N * 4 to be usable), owned by the caller, one per stream; NULL = never split.
+     * split_k: 0 = automatic, 1 = never, > 1 = exactly this many ranges (DWM_EUNSUPPORTED if impossible); when: see `tile`. */
     void* workspace; int64_t workspace_bytes; int32_t split_k;
     /* fp32 residual stream (RESID, res_mod == 0): when C32 != NULL, `res` and `blend` are fp32 matrices (ld_res / ld_blend in
      * fp32 elements, rows through c_map like C), the result v is written to C32 in fp32 (in place over `res` or `blend` allowed)
@@ -121,19 +120,32 @@ typedef struct dwm_gemm_args {
      * and so its error - is the same at every denoise step) and the hidden / context streams of the MMDiT forward
      * (src/dwm/models/crossview_temporal_dit.py:486-598: ~130 residual adds per forward). */
     void* C32; int64_t ldc32;
-    /* tile configuration: 0 = automatic, 1 = 256 x 256 x 64 tiles (one 8-wave workgroup per CU), 2 = 256 x 128 x 32 tiles
-     * (two 4-wave workgroups per CU; chosen automatically where it cuts the padded columns, e.g. N = 320 / 640; not with
-     * C32; split-K grids keep the 256 x 256 tile), 3 = automatic and the 4-wave kernels (gemm_bf16_4w.hip) may serve the launch,
-     * 4 = as 3, their fast form only (A/B measurements) */
+    /* tile configuration: 0 = automatic, 1 = 256 x 256 x 64 tiles (one 8-wave workgroup per CU), 2 = 256 x 128 x 32 tiles (two
+     * 4-wave workgroups per CU), 3 = automatic and the 4-wave kernels (gemm_bf16_4w.hip) may serve the launch (what the MMDiT
+     * inference forward and train step pass; the Python host side maps DWM_GEMM4W=1 / 0 / f to tile 3 / 0 / 4 per call - the library
+     * reads no environment), 4 = as 3, their fast form only (A/B measurements).
+     * Which kernel serves a launch, in order of precedence (plan_gemm in gemm_bf16.hip; tile 3 / 4 count as 0 from step 2 on):
+     *   1. 4-wave (256 x 256 x 64 tile, one wave per SIMD; 412 against 434 ms per denoise step, profiles/README.md): tile 3 / 4,
+     *      lda % 64 == 0, K >= 128, no output row map, no split-K asked for or due by the automatic rule of step 3 (judged without
+     *      looking at the workspace's alignment or size), epilogue operand leading dimensions < 2^31; RESID: a residual and
+     *      res_mod <= 0, no activation, operands residual / gate + residual / residual + blend, C32 without a bf16 mirror.
+     *      Fast form: no A row map, no taps, M % 256 == N % 256 == 0, res_mod == 0.  General form (tile 3 only): ragged M / N, an
+     *      A row map, taps, the per-image residual row (res_mod < 0, bf16 residual alone).  A launch served here skips step 2.
+     *   2. the remaining argument checks (row maps, ntaps <= 27, k_per_tap, row divisors <= 2^30, lda >= k_per_tap, tile in 0..2).
+     *   3. split-K (8-wave, 256 x 256 tiles): split_k > 1, or split_k == 0 with PLAIN / RESID, no C32, a 16-byte aligned workspace, at
+     *      most 128 tiles (less than half of the CUs) and K / 64 >= 16: 256 / tiles ranges; then at least 8 K steps per range, at
+     *      most 32 ranges and what workspace_bytes holds.  Fewer than 2 ranges left: DWM_EUNSUPPORTED if asked for, else unsplit.
+     *   4. 8-wave 256 x 128 tiles: tile == 2, or tile == 0 without C32 where they pad fewer columns (e.g. N = 320 / 640) and
+     *      K <= 640; with C32 DWM_EUNSUPPORTED.  Otherwise 8-wave 256 x 256 tiles.
+     *   5. within 4: the FAST kernels (no output row map, leading dimensions < 2^31; RESID: no activation, res_mod == 0 or the bf16
+     *      per-image residual row alone), with the RESID operand set residual / gate + residual / residual + blend (/ per-image
+     *      residual row) known at compile time; every other launch the general kernels. */
     int32_t tile;
 } dwm_gemm_args;
 
 int dwm_gemm_bf16(const dwm_gemm_args* args, void* stream);
-/* args->tile == 3 ("automatic, 4-wave kernels allowed": what the MMDiT inference forward passes): launches without row maps / taps /
- * split-K and with M % 256 == N % 256 == 0, K % 64 == 0, K >= 128 run the same epilogues on a 4-wave main loop (gemm_bf16_4w.hip; 412
- * against 434 ms per denoise step, profiles/README.md); every other caller keeps the 8-wave kernels, on which the whole GPU suite
- * has run.  (The library reads no environment: the Python host side maps DWM_GEMM4W=1 / 0 / f to tile 3 / 0 / 4 per call.)  This counts
- * the launches served (a relaxed atomic: diagnostics, the library's only process-wide mutable state besides lazily set kernel attributes). */
+/* Launches the 4-wave kernels served (step 1 of the rule at dwm_gemm_args.tile), whatever their status (a relaxed atomic: diagnostics,
+ * the library's only process-wide mutable state besides lazily set kernel attributes). */
 int64_t dwm_gemm4w_launches(void);
 /* ... and how many of them ran the general form of those kernels (ragged M / N, A row map, taps, per-image residual row). */
 int64_t dwm_gemm4w_launches_general(void);

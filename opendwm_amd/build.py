@@ -56,7 +56,8 @@ def source_hash() -> str:
 
 def build(force: bool = False, verbose: bool = False) -> str:
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "attention_common.h"), os.path.join(INCLUDE, "dwm_hip.h")]
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "attention_common.h"), os.path.join(CSRC, "gemm_common.h"),
+               os.path.join(INCLUDE, "dwm_hip.h")]
     shash = source_hash()
     stamp = os.path.join(CSRC, "build", ".source_hash")
     objdir = os.path.join(CSRC, "build")

@@ -21,10 +21,11 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
-#include "dwm_hip.h"
+#include "gemm_common.h"
 
 namespace {
+
+using namespace dwm_gemm;
 
 // dwm_gemm_args.reserved carries ablation / tuning knobs of development builds (-DDWM_DEV_HOOKS: bit 0 main loop without
 // epilogue, bit 1 no stores, bit 2 general instead of FAST kernels, bits 4-8 group height, bit 9 the 256 x 128 tile, bit 10 pad its LDS); the shipped object ignores it
@@ -57,11 +58,6 @@ template <> struct TileCfg<1> { static constexpr int bm = 256, bn = 128, bk = 32
 template <int TC> constexpr int tile_lds_bytes() { return (TileCfg<TC>::ast * TileCfg<TC>::bm + TileCfg<TC>::wst * TileCfg<TC>::bn) * TileCfg<TC>::bk * 2; }
 static_assert(tile_lds_bytes<0>() == LDS_BYTES && 2 * tile_lds_bytes<1>() <= 160 * 1024, "LDS budget");
 
-struct DevRowMap {
-    FastDiv rw, rh;
-    int64_t rpitch, ipitch, origin;
-    int enabled, xstep;
-};
 struct ConvParams {
     DevRowMap a, c;
     int steps_per_tap;          // k_per_tap / BK
@@ -77,40 +73,7 @@ struct ConvParams {
     int gm;
     FastDiv fd_pergroup, fd_gm;
 };
-// group height: 8 row tiles share a W panel in the XCD's L2 for K ~ 1.5 k; a long K (FF2: 6144) makes the A panel of
-// 8 rows (25 MB) stream through it, 4 rows measured 3 % faster there
-static inline void set_raster(ConvParams& cp, const dwm_gemm_args& a, int ntn) {
-    int gm = (DWM_RESERVED(a.reserved) >> 4) & 31;
-    if (gm == 0) gm = a.K >= 4096 ? 4 : 8;
-    cp.gm = gm;
-    cp.fd_pergroup = make_fastdiv((uint32_t)(gm * ntn));
-    cp.fd_gm = make_fastdiv((uint32_t)gm);
-}
-// a dwm_rowmap2d with its divisions prepared (false: not a valid map)
-static inline bool make_dev_rowmap(const dwm_rowmap2d& r, DevRowMap& d) {
-    d.enabled = r.rw > 0;
-    d.xstep = r.xstep > 0 ? (int)r.xstep : 1;
-    if (!d.enabled) { d.rw = make_fastdiv(1); d.rh = make_fastdiv(1); d.rpitch = d.ipitch = d.origin = 0; return true; }
-    if (r.rh <= 0 || r.rw >= (1ll << 30) || r.rh >= (1ll << 30)) return false;
-    d.rw = make_fastdiv((uint32_t)r.rw); d.rh = make_fastdiv((uint32_t)r.rh);
-    d.rpitch = r.rpitch; d.ipitch = r.ipitch; d.origin = r.origin;
-    return true;
-}
-// K steps per tap (256 x 256 x 64 tiles) and the RESID row divisors
-static inline void set_dividers(ConvParams& cp, const dwm_gemm_args& a, int64_t kpt) {
-    cp.steps_per_tap = (int)(kpt / BK);
-    cp.fd_steps = make_fastdiv((uint32_t)cp.steps_per_tap);
-    cp.fd_rpg = make_fastdiv((uint32_t)(a.rows_per_gate > 0 ? a.rows_per_gate : 1));
-    cp.fd_rmod = make_fastdiv((uint32_t)(a.res_mod > 0 ? a.res_mod : a.res_mod < 0 ? -a.res_mod : 1));
-    cp.fd_rpa = make_fastdiv((uint32_t)(a.rows_per_alpha > 0 ? a.rows_per_alpha : 1));
-}
 constexpr int EPI_SPLITK = 100;    // internal epilogue id: fp32 partials to the workspace
-DWM_DEVINL int64_t map_row(const DevRowMap& rm, int64_t m) {
-    if (!rm.enabled) return m;
-    const uint32_t q = fdiv((uint32_t)m, rm.rw), x = (uint32_t)m - q * rm.rw.d;
-    const uint32_t i = fdiv(q, rm.rh), y = q - i * rm.rh.d;
-    return (int64_t)i * rm.ipitch + (int64_t)y * rm.rpitch + (int64_t)x * rm.xstep + rm.origin;
-}
 
 // FAST: the linear layers of the transformer blocks - no output row map, every leading dimension < 2^31, and for RESID:
 // residual row = output row, no activation - with those facts known at compile time: the per-step address arithmetic is
@@ -959,22 +922,213 @@ f32_finish_kernel(const dwm_gemm_args p, const ConvParams cp) {
     *(float4*)(o + 4) = make_float4(v[4], v[5], v[6], v[7]);
 }
 
+// ---- host side: argument checks (shared by dwm_gemm_bf16 and dwm_gemm_f32), plan, parameter block, launch
+
+// What differs between the argument checks of the two entry points.  KNOWN asymmetries, kept as found (callers see the codes).
+struct GemmFlavor {
+    int quantum;            // elements per 16 bytes: what the leading dimensions of the epilogue operands are multiples of
+    int64_t m_limit;        // M stays below it
+    int too_many_taps;      // the code for ntaps > 27
+    bool fp32;              // dwm_gemm_f32: does not read C32
+};
+constexpr GemmFlavor kBf16 = {8, 1ll << 31, DWM_EINVAL, false};
+constexpr GemmFlavor kFp32 = {4, 1ll << 30, DWM_EUNSUPPORTED, true};
+
+int check_sizes(const dwm_gemm_args& a, const GemmFlavor& fl) {
+    if (a.M <= 0 || a.N <= 0 || a.K <= 0 || a.M >= fl.m_limit || a.N >= (1ll << 31)) return DWM_EINVAL;
+    if (a.K % BK != 0 || a.N % 8 != 0) return DWM_EUNSUPPORTED;
+    return DWM_OK;
+}
+// the operands of the epilogue (with C32 the residual and blend rows are fp32 whichever entry point reads them)
+int check_epilogue(const dwm_gemm_args& a, const GemmFlavor& fl) {
+    const int q = fl.quantum, q_stream = a.C32 ? 4 : q;
+    switch (a.epilogue) {
+        case DWM_EPI_PLAIN: return DWM_OK;
+        case DWM_EPI_GEGLU: return a.N % 64 != 0 ? DWM_EUNSUPPORTED : DWM_OK;
+        case DWM_EPI_RESID:
+            if (a.gate && (a.rows_per_gate <= 0 || a.ld_gate % q != 0 || !dwm_aligned16(a.gate))) return DWM_EINVAL;
+            if (a.res && (a.ld_res % q_stream != 0 || !dwm_aligned16(a.res))) return DWM_EALIGN;
+            if (a.blend && (a.alpha == nullptr || a.rows_per_alpha <= 0 || a.ld_blend % q_stream != 0 || !dwm_aligned16(a.blend))) return DWM_EINVAL;
+            if (a.gate && a.blend) return DWM_EUNSUPPORTED;        // one register set carries the gate OR the blend rows
+            if (!fl.fp32 && a.C32 != nullptr && (a.ldc32 % 4 != 0 || a.ldc32 < a.N || !dwm_aligned16(a.C32) || a.res_mod != 0 || a.split_k > 1))
+                return DWM_EINVAL;
+            return DWM_OK;
+        case DWM_EPI_RMSHEAD: return a.rms_w == nullptr || a.rms_ncols % 64 != 0 || a.N % 64 != 0 ? DWM_EINVAL : DWM_OK;
+        default: return DWM_EINVAL;
+    }
+}
+int check_taps(const dwm_gemm_args& a, const GemmFlavor& fl) {
+    const int ntaps = gemm_ntaps(a);
+    if (ntaps > 27) return fl.too_many_taps;
+    const int64_t kpt = gemm_k_per_tap(a);
+    return kpt <= 0 || kpt % BK != 0 || kpt * ntaps != a.K ? DWM_EINVAL : DWM_OK;
+}
+// the row divisors are 32-bit fast divisors
+int check_row_divisors(const dwm_gemm_args& a) {
+    return a.rows_per_gate > (1ll << 30) || a.res_mod > (1ll << 30) || a.res_mod < -(1ll << 30) || a.rows_per_alpha > (1ll << 30) ? DWM_EINVAL : DWM_OK;
+}
+bool valid_rowmaps(const dwm_gemm_args& a) {
+    DevRowMap d;
+    return make_dev_rowmap(a.a_map, d) && make_dev_rowmap(a.c_map, d);
+}
+
+// The selection rule of dwm_gemm_bf16, in order of precedence (host arithmetic only; include/dwm_hip.h repeats it at
+// dwm_gemm_args.tile).  `a` has passed the checks of dwm_gemm_bf16 up to the epilogue operands and has tile 3 / 4 normalised to 0;
+// `tile_asked` is the caller's value.  Reserved bits count in -DDWM_DEV_HOOKS builds only.
+//   1. 4-wave (gemm_bf16_4w.hip): tile_asked 3 / 4, lda % 64 == 0, no reserved bit set, and dwm_gemm4w_covers() accepts (see there:
+//      no output row map, no split-K asked for or due by the automatic rule, K >= 128, ...): W4_FAST for M % 256 == N % 256 == 0
+//      without A row map, taps or the per-image residual row, else - tile_asked 3 only - W4_GENERAL.  A launch served here does
+//      not see the checks of 2.
+//   2. the remaining argument checks - row maps, ntaps <= 27, k_per_tap, the 2^30 limits of the row divisors, lda >= k_per_tap,
+//      tile in 0..2 - all DWM_EINVAL.
+//   3. split-K (W8_SPLITK, 256 x 256 tiles): split_k > 1 (DWM_EUNSUPPORTED unless PLAIN / RESID, a 16-byte aligned workspace, no C32
+//      and reserved bits 0 / 1 clear), or split_k == 0 and auto_splitk() (a small tile grid, a long K) under the same conditions:
+//      256 / tiles ranges.  Clamped to >= 8 K steps per range, 32 ranges and the workspace size; fewer than 2 ranges left:
+//      DWM_EUNSUPPORTED when asked for, otherwise the launch goes on unsplit with 4.
+//   4. the tile: 256 x 128 (W8_128) for tile == 2, for tile == 0 without C32 where it pads fewer columns and K <= 640 (N = 320 -> 384
+//      instead of 512: the SD 2.1 UNet's first level; measured, profiles/README.md: N = 320, K = 320: 1.17 x; with K >= 2880 the
+//      256 x 256 main loop wins although it pads more), and for reserved bit 9; with C32 that is DWM_EUNSUPPORTED.  Else 256 x 256.
+//   5. FAST (the transformer blocks' linear layers, see gemm_bf16_kernel): no output row map, ldc < 2^31, reserved bit 2 clear; RESID
+//      also: no activation, operand leading dimensions < 2^31, res_mod == 0 or the bf16 per-image residual row alone (RS 18).
+//   6. C32 (W8_C32, the fp32 residual stream): FAST needs ldc32 < 2^31 as well; FAST with residual / gate + residual / residual +
+//      blend and no bf16 mirror takes the compile-time operand form (RS 2 / 3 / 6), every other operand set RS 0.
+//   7. W8_256 / W8_128, epilogue and FAST as found; FAST RESID with RS 2 / 3 / 6 / 18 takes the compile-time operand form.
+// The raster group height is raster_group_height(K) unless reserved bits 4-8 give one.
+int plan_gemm(const dwm_gemm_args& a, int tile_asked, GemmPlan& plan) {
+    const int knobs = DWM_RESERVED(a.reserved);
+    if ((tile_asked == 3 || tile_asked == 4) && !knobs && a.lda % 64 == 0 && dwm_gemm4w_covers(a, tile_asked == 4, plan)) return DWM_OK;
+
+    if (!valid_rowmaps(a)) return DWM_EINVAL;
+    int rc = check_taps(a, kBf16);
+    if (rc == DWM_OK) rc = check_row_divisors(a);
+    if (rc != DWM_OK) return rc;
+    if (a.lda < gemm_k_per_tap(a)) return DWM_EINVAL;
+    if (a.tile < 0 || a.tile > 2) return DWM_EINVAL;
+
+    plan = GemmPlan();
+    plan.epi = a.epilogue;
+    plan.ntm = (int)((a.M + BM - 1) / BM); plan.ntn = (int)((a.N + BN - 1) / BN);
+    plan.block = 512; plan.lds = LDS_BYTES;
+    plan.gm = (knobs >> 4) & 31;
+    if (plan.gm == 0) plan.gm = raster_group_height(a.K);
+
+    const int64_t tiles = (int64_t)plan.ntm * plan.ntn, nk = a.K / BK;
+    const bool ws_usable = dwm_aligned16(a.workspace) && !(knobs & 3);
+    int ksplit = 1;
+    if (a.split_k > 1) {
+        if (!((a.epilogue == DWM_EPI_PLAIN || a.epilogue == DWM_EPI_RESID) && a.workspace != nullptr && a.C32 == nullptr && ws_usable))
+            return DWM_EUNSUPPORTED;
+        ksplit = a.split_k;
+    } else if (auto_splitk(a, tiles) && ws_usable) {
+        ksplit = (int)(256 / tiles);
+    }
+    if (ksplit > 1) {
+        ksplit = clamp_ksplit(ksplit, nk, 32, a.M * a.N * 4, a.workspace_bytes);
+        if (ksplit < 2) {
+            if (a.split_k > 1) return DWM_EUNSUPPORTED;
+            ksplit = 1;
+        }
+    }
+    plan.ksplit = ksplit;
+    if (ksplit > 1) {
+        plan.family = GemmFamily::W8_SPLITK;
+        plan.epi = EPI_SPLITK;
+        plan.grid = (unsigned)(plan.ntm * plan.ntn * ksplit);
+        return DWM_OK;
+    }
+
+    plan.tc = a.tile == 2 ? 1 : 0;
+    if (a.tile == 0 && a.C32 == nullptr) {
+        const int64_t c256 = (a.N + 255) / 256 * 256, c128 = (a.N + 127) / 128 * 128;
+        if (c128 < c256 && a.K <= 640) plan.tc = 1;
+    }
+    if (knobs & 0x200) plan.tc = 1;
+    if (plan.tc == 1) {
+        if (a.C32 != nullptr) return DWM_EUNSUPPORTED;
+        plan.ntn = (int)((a.N + TileCfg<1>::bn - 1) / TileCfg<1>::bn);
+        plan.block = TileCfg<1>::nwaves * 64;
+        plan.lds = tile_lds_bytes<1>() + ((knobs & 0x400) ? DWM_DEV_LDS_PAD : 0);
+    }
+    plan.grid = (unsigned)(plan.ntm * plan.ntn);
+
+    const int64_t lim = 1ll << 31;
+    const int rs16 = (a.gate ? 1 : 0) | (a.res ? 2 : 0) | (a.blend ? 4 : 0) | ((a.res && a.res_mod < 0) ? 16 : 0);
+    plan.fast = a.c_map.rw <= 0 && a.ldc < lim && !(knobs & 4);
+    if (a.epilogue == DWM_EPI_RESID)
+        plan.fast = plan.fast && (a.res_mod == 0 || (rs16 == 18 && a.C32 == nullptr)) && a.act == DWM_ACT_NONE &&
+                    (a.gate == nullptr || a.ld_gate < lim) && (a.res == nullptr || a.ld_res < lim) && (a.blend == nullptr || a.ld_blend < lim);
+    if (a.C32 != nullptr) {
+        plan.family = GemmFamily::W8_C32;
+        plan.rf32 = true;
+        plan.fast = plan.fast && a.ldc32 < lim;
+        const int rs = rs16 | (a.C ? 8 : 0);                   // (res_mod == 0 here: bit 16 is clear)
+        plan.rs = plan.fast && (rs == 2 || rs == 3 || rs == 6) ? rs : 0;
+        return DWM_OK;
+    }
+    plan.family = plan.tc == 1 ? GemmFamily::W8_128 : GemmFamily::W8_256;
+    plan.rs = a.epilogue == DWM_EPI_RESID && plan.fast && (rs16 == 2 || rs16 == 3 || rs16 == 6 || rs16 == 18) ? rs16 : 0;
+    return DWM_OK;
+}
+
+// the parameter block of the 8-wave kernels for a planned launch (row maps checked by the caller)
+void fill_conv_params(const dwm_gemm_args& a, const GemmPlan& pl, ConvParams& cp) {
+    make_dev_rowmap(a.a_map, cp.a);
+    make_dev_rowmap(a.c_map, cp.c);
+    cp.steps_per_tap = (int)(gemm_k_per_tap(a) / (pl.tc == 1 ? TileCfg<1>::bk : BK));
+    cp.fd_steps = make_fastdiv((uint32_t)cp.steps_per_tap);
+    cp.fd_rpg = make_fastdiv((uint32_t)(a.rows_per_gate > 0 ? a.rows_per_gate : 1));
+    cp.fd_rmod = make_fastdiv((uint32_t)(a.res_mod > 0 ? a.res_mod : a.res_mod < 0 ? -a.res_mod : 1));
+    cp.fd_rpa = make_fastdiv((uint32_t)(a.rows_per_alpha > 0 ? a.rows_per_alpha : 1));
+    for (int t = 0; t < 27; ++t) cp.tap_shift[t] = t < a.ntaps ? a.tap_shift[t] : 0;
+    cp.ksplit = pl.ksplit;
+    cp.ws = (float*)a.workspace;
+    cp.ws_slice = a.M * a.N;
+    cp.gm = pl.gm;
+    cp.fd_pergroup = make_fastdiv((uint32_t)(pl.gm * pl.ntn));
+    cp.fd_gm = make_fastdiv((uint32_t)pl.gm);
+}
+
+// ---- launch: allow8w raises the dynamic-LDS limit of ONE kernel (development builds: room for the pad of reserved bit 10), enqueue8w
+// puts it on the stream with the plan's geometry, launch8w = both + the launch status
+template <int EPI, bool FAST, bool RF32, int TC, int RS>
+hipError_t allow8w() {
+    return dwm_allow_dynamic_lds<gemm_bf16_kernel<EPI, FAST, RF32, TC, RS>>(tile_lds_bytes<TC>() + (TC ? DWM_DEV_LDS_PAD : 0));
+}
+template <int EPI, bool FAST, bool RF32, int TC, int RS>
+void enqueue8w(const dwm_gemm_args& a, const ConvParams& cp, const GemmPlan& pl, hipStream_t s) {
+    hipLaunchKernelGGL((gemm_bf16_kernel<EPI, FAST, RF32, TC, RS>), dim3(pl.grid), dim3(pl.block), pl.lds, s, a, cp, pl.ntm, pl.ntn);
+}
+template <int EPI, bool FAST, bool RF32, int TC, int RS>
+int launch8w(const dwm_gemm_args& a, const ConvParams& cp, const GemmPlan& pl, hipStream_t s) {
+    const hipError_t e = allow8w<EPI, FAST, RF32, TC, RS>();
+    if (e != hipSuccess) return (int)e;
+    enqueue8w<EPI, FAST, RF32, TC, RS>(a, cp, pl, s);
+    return dwm_launch_status();
+}
+
+int launch_splitk(const dwm_gemm_args& a, const ConvParams& cp, const GemmPlan& pl, hipStream_t s) {
+    const hipError_t e = allow8w<EPI_SPLITK, false, false, 0, 0>();
+    if (e != hipSuccess) return (int)e;
+    enqueue8w<EPI_SPLITK, false, false, 0, 0>(a, cp, pl, s);
+    const int64_t nthr = a.M * (a.N >> 3);
+    hipLaunchKernelGGL(splitk_finish_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, a, cp);
+    return dwm_launch_status();
+}
 }  // namespace
 
 extern "C" int dwm_gemm_f32(const dwm_gemm_args* a, void* stream) {
     if (a == nullptr || a->A == nullptr || a->W == nullptr || a->C == nullptr || a->workspace == nullptr) return DWM_EINVAL;
-    if (a->M <= 0 || a->N <= 0 || a->K <= 0 || a->M >= (1ll << 30) || a->N >= (1ll << 31)) return DWM_EINVAL;
-    if (a->K % BK != 0 || a->N % 8 != 0) return DWM_EUNSUPPORTED;
+    int rc = check_sizes(*a, kFp32);
+    if (rc != DWM_OK) return rc;
     // implicit convolution (a_map / c_map / taps as in dwm_gemm_bf16): every tap is walked as three plane taps (A_hi x W_hi, A_hi x
     // W_lo, A_lo x W_hi), so 9 taps (a 3x3 kernel) fill the 27 tap slots of one main-loop launch; W is [N, ntaps * 3 * k_per_tap]
     // (ops.split_weight).  More taps (the 27 of a causal 3x3x3 convolution: the temporal VAE) run as GROUPS of 9 - one main-loop
     // launch per group, each into its own fp32 partial slices, all summed in order by the one finishing kernel; W then holds the
     // groups one after the other, group g = [N, taps_g * 3 * k_per_tap] contiguous.
-    const int ctaps = a->ntaps > 0 ? a->ntaps : 1;
-    if (ctaps > 27) return DWM_EUNSUPPORTED;
-    const int ngroups = (ctaps + 8) / 9;
-    const int64_t kpt = a->ntaps > 0 ? a->k_per_tap : a->K;
-    if (kpt <= 0 || kpt % BK != 0 || kpt * ctaps != a->K) return DWM_EINVAL;
+    rc = check_taps(*a, kFp32);
+    if (rc != DWM_OK) return rc;
+    const int ctaps = gemm_ntaps(*a), ngroups = (ctaps + 8) / 9;
+    const int64_t kpt = gemm_k_per_tap(*a);
     // rows of the A buffer (both planes cover all of them: taps reach into the padded border)
     int64_t a_rows = a->M;
     if (a->a_map.rw > 0) {
@@ -983,43 +1137,36 @@ extern "C" int dwm_gemm_f32(const dwm_gemm_args* a, void* stream) {
         // one past the last row any tap of any output pixel reads (every grid of opendwm_amd.ops ends exactly there: PaddedGrid
         // and its stride-2 maps, TimeGrid, and Grid3D, whose two context frames sit in FRONT of the mapped images)
         int64_t reach = 0;
-        for (int t = 0; t < ctaps && a->ntaps > 0; ++t) reach = a->tap_shift[t] > reach ? a->tap_shift[t] : reach;
+        for (int t = 0; t < a->ntaps; ++t) reach = a->tap_shift[t] > reach ? a->tap_shift[t] : reach;
         a_rows = a->a_map.origin + (a->M / ppi - 1) * a->a_map.ipitch + (a->a_map.rh - 1) * a->a_map.rpitch +
                  (a->a_map.rw - 1) * (a->a_map.xstep > 0 ? a->a_map.xstep : 1) + reach + 1;
         if (a_rows <= 0) return DWM_EINVAL;
-    } else if (a->ntaps > 0) return DWM_EUNSUPPORTED;            // taps need the padded-grid map
+    } else if (a->ntaps > 0) return DWM_EUNSUPPORTED;            // taps need the padded-grid map (known asymmetry: bf16 taps do not)
     if (a->lda % 4 != 0 || a->ldc % 4 != 0 || !dwm_aligned16(a->A) || !dwm_aligned16(a->W) || !dwm_aligned16(a->C) ||
         !dwm_aligned16(a->workspace)) return DWM_EALIGN;
-    const int64_t nout = a->epilogue == DWM_EPI_GEGLU ? a->N / 2 : a->N;
+    const int64_t nout = gemm_nout(*a);
     if (a->ldc < nout || a->lda < kpt) return DWM_EINVAL;
-    switch (a->epilogue) {
-        case DWM_EPI_PLAIN: break;
-        case DWM_EPI_GEGLU: if (a->N % 64 != 0) return DWM_EUNSUPPORTED; break;
-        case DWM_EPI_RESID:
-            if (a->gate && (a->rows_per_gate <= 0 || a->ld_gate % 4 != 0 || !dwm_aligned16(a->gate))) return DWM_EINVAL;
-            if (a->res && (a->ld_res % 4 != 0 || !dwm_aligned16(a->res))) return DWM_EALIGN;
-            if (a->blend && (a->alpha == nullptr || a->rows_per_alpha <= 0 || a->ld_blend % 4 != 0 || !dwm_aligned16(a->blend))) return DWM_EINVAL;
-            if (a->gate && a->blend) return DWM_EUNSUPPORTED;
-            break;
-        case DWM_EPI_RMSHEAD: if (a->rms_w == nullptr || a->rms_ncols % 64 != 0 || a->N % 64 != 0) return DWM_EINVAL; break;
-        default: return DWM_EINVAL;
-    }
-    if (a->rows_per_gate > (1ll << 30) || a->res_mod > (1ll << 30) || a->res_mod < -(1ll << 30) || a->rows_per_alpha > (1ll << 30)) return DWM_EINVAL;
-    // workspace: [A_hi ; A_lo] bf16 planes, then the fp32 partial sums
+    rc = check_epilogue(*a, kFp32);
+    if (rc == DWM_OK) rc = check_row_divisors(*a);
+    if (rc != DWM_OK) return rc;
+    if (!valid_rowmaps(*a)) return DWM_EINVAL;
+    // workspace: [A_hi ; A_lo] bf16 planes, then the fp32 partial sums of `ksplit` K ranges per group (one launch, W8_SPLITK, each)
+    GemmPlan pl = GemmPlan();
+    pl.family = GemmFamily::W8_SPLITK; pl.epi = EPI_SPLITK;
+    pl.ntm = (int)((a->M + BM - 1) / BM); pl.ntn = (int)((a->N + BN - 1) / BN);
     const int64_t plane_bytes = ((2 * a_rows * kpt * 2 + 255) / 256) * 256;
-    const int ntm = (int)((a->M + BM - 1) / BM), ntn = (int)((a->N + BN - 1) / BN);
     // (K ranges per launch: chosen for the shortest group, so that every range of every group has K steps)
     const int last_taps = ctaps - 9 * (ngroups - 1);
-    const int64_t tiles = (int64_t)ntm * ntn, nk = 3 * kpt * last_taps / BK, slice_bytes = a->M * a->N * 4;
-    int ksplit = 1;
-    if (tiles * ngroups <= 128 && nk >= 16) {
-        ksplit = (int)(256 / (tiles * ngroups));
-        if (ksplit > nk / 8) ksplit = (int)(nk / 8);
-        if (ksplit > 32 / ngroups) ksplit = 32 / ngroups;
-        if (ksplit < 1) ksplit = 1;
-    }
-    while (ksplit > 1 && plane_bytes + (int64_t)ngroups * ksplit * slice_bytes > a->workspace_bytes) --ksplit;
+    const int64_t tiles = (int64_t)pl.ntm * pl.ntn, nk = 3 * kpt * last_taps / BK, slice_bytes = a->M * a->N * 4;
+    pl.ksplit = 1;
+    if (splitk_pays(tiles * ngroups, nk))
+        pl.ksplit = clamp_ksplit((int)(256 / (tiles * ngroups)), nk, 32 / ngroups, ngroups * slice_bytes, a->workspace_bytes - plane_bytes);
+    if (pl.ksplit < 1) pl.ksplit = 1;
     if (plane_bytes + (int64_t)ngroups * slice_bytes > a->workspace_bytes) return DWM_EINVAL;
+    pl.grid = (unsigned)(pl.ntm * pl.ntn * pl.ksplit); pl.block = 512; pl.lds = LDS_BYTES;
+
+    const hipError_t e = allow8w<EPI_SPLITK, false, false, 0, 0>();
+    if (e != hipSuccess) return (int)e;
     hipStream_t s = (hipStream_t)stream;
     bf16_t* planes = (bf16_t*)a->workspace;
     {
@@ -1029,30 +1176,25 @@ extern "C" int dwm_gemm_f32(const dwm_gemm_args* a, void* stream) {
     }
     dwm_gemm_args g = *a;
     g.A = planes; g.lda = kpt;
-    ConvParams cp;
-    if (!make_dev_rowmap(a->a_map, cp.a) || !make_dev_rowmap(a->c_map, cp.c)) return DWM_EINVAL;
-    set_dividers(cp, *a, kpt);
-    cp.ksplit = ksplit;
-    float* const ws_base = (float*)((char*)a->workspace + plane_bytes);
-    cp.ws_slice = a->M * a->N;
-    const hipError_t e = dwm_allow_dynamic_lds<gemm_bf16_kernel<EPI_SPLITK>>(LDS_BYTES);
-    if (e != hipSuccess) return (int)e;
     g.reserved = 0;
+    float* const ws_base = (float*)((char*)a->workspace + plane_bytes);
+    ConvParams cp;
     for (int gi = 0; gi < ngroups; ++gi) {
         const int tg = gi + 1 < ngroups ? 9 : last_taps;
         g.K = 3 * kpt * tg;
         g.W = (const bf16_t*)a->W + (int64_t)a->N * (3 * kpt * 9) * gi;
+        pl.gm = raster_group_height(g.K);
+        fill_conv_params(*a, pl, cp);
         for (int t = 0; t < 27; ++t) cp.tap_shift[t] = 0;
         for (int t = 0; t < tg; ++t) {                // per tap: A_hi (x W_hi), A_hi (x W_lo), A_lo (x W_hi)
             const int64_t sh = a->ntaps > 0 ? a->tap_shift[9 * gi + t] : 0;
             cp.tap_shift[3 * t] = sh; cp.tap_shift[3 * t + 1] = sh; cp.tap_shift[3 * t + 2] = sh + a_rows;
         }
-        cp.ws = ws_base + (int64_t)gi * ksplit * cp.ws_slice;
-        set_raster(cp, g, ntn);
-        hipLaunchKernelGGL(gemm_bf16_kernel<EPI_SPLITK>, dim3((unsigned)(ntm * ntn * ksplit)), dim3(512), LDS_BYTES, s, g, cp, ntm, ntn);
+        cp.ws = ws_base + (int64_t)gi * pl.ksplit * cp.ws_slice;
+        enqueue8w<EPI_SPLITK, false, false, 0, 0>(g, cp, pl, s);
     }
     cp.ws = ws_base;
-    cp.ksplit = ngroups * ksplit;                     // the finishing kernel sums every range of every group, in order
+    cp.ksplit = ngroups * pl.ksplit;                  // the finishing kernel sums every range of every group, in order
     const int64_t nthr = a->M * (nout >> 3);
     const dim3 fg((unsigned)((nthr + 255) / 256));
     switch (a->epilogue) {
@@ -1064,195 +1206,78 @@ extern "C" int dwm_gemm_f32(const dwm_gemm_args* a, void* stream) {
     return dwm_launch_status();
 }
 
-// gemm_bf16_4w.hip: the 4-wave main loop under the same epilogues (dwm_gemm_args.tile == 3 / 4); -1 = not a launch it covers
-int dwm_gemm4w_try(const dwm_gemm_args* a, void* stream, bool fast_only);
+namespace {
+
+// (the launch functions from here on follow dwm_gemm_f32, and the cases of launch_c32 stand in this order, because the compiler emits the
+// kernels in the order of their first use: this keeps the device code of this file identical, line for line, to what it was)
+int launch_c32(const dwm_gemm_args& a, const ConvParams& cp, const GemmPlan& pl, hipStream_t s) {
+    if (!pl.fast) return launch8w<DWM_EPI_RESID, false, true, 0, 0>(a, cp, pl, s);
+    switch (pl.rs) {
+        case 0: return launch8w<DWM_EPI_RESID, true, true, 0, 0>(a, cp, pl, s);
+        case 3: return launch8w<DWM_EPI_RESID, true, true, 0, 3>(a, cp, pl, s);
+        case 2: return launch8w<DWM_EPI_RESID, true, true, 0, 2>(a, cp, pl, s);
+        default: return launch8w<DWM_EPI_RESID, true, true, 0, 6>(a, cp, pl, s);
+    }
+}
+// bf16 RESID, FAST, the operand set at compile time
+template <int TC>
+int launch_resid_rs(const dwm_gemm_args& a, const ConvParams& cp, const GemmPlan& pl, hipStream_t s) {
+    switch (pl.rs) {
+        case 2: return launch8w<DWM_EPI_RESID, true, false, TC, 2>(a, cp, pl, s);
+        case 3: return launch8w<DWM_EPI_RESID, true, false, TC, 3>(a, cp, pl, s);
+        case 6: return launch8w<DWM_EPI_RESID, true, false, TC, 6>(a, cp, pl, s);
+        default: return launch8w<DWM_EPI_RESID, true, false, TC, 18>(a, cp, pl, s);
+    }
+}
+template <int EPI>
+int launch_epi(const dwm_gemm_args& a, const ConvParams& cp, const GemmPlan& pl, hipStream_t s) {
+    if (pl.fast) return pl.tc == 1 ? launch8w<EPI, true, false, 1, 0>(a, cp, pl, s) : launch8w<EPI, true, false, 0, 0>(a, cp, pl, s);
+    return pl.tc == 1 ? launch8w<EPI, false, false, 1, 0>(a, cp, pl, s) : launch8w<EPI, false, false, 0, 0>(a, cp, pl, s);
+}
+// W8_256 / W8_128
+int launch_tile(const dwm_gemm_args& a, const ConvParams& cp, const GemmPlan& pl, hipStream_t s) {
+    if (pl.rs != 0) return pl.tc == 1 ? launch_resid_rs<1>(a, cp, pl, s) : launch_resid_rs<0>(a, cp, pl, s);
+    switch (pl.epi) {
+        case DWM_EPI_PLAIN: return launch_epi<DWM_EPI_PLAIN>(a, cp, pl, s);
+        case DWM_EPI_GEGLU: return launch_epi<DWM_EPI_GEGLU>(a, cp, pl, s);
+        case DWM_EPI_RESID: return launch_epi<DWM_EPI_RESID>(a, cp, pl, s);
+        default: return launch_epi<DWM_EPI_RMSHEAD>(a, cp, pl, s);
+    }
+}
+
+}  // namespace
 
 extern "C" int dwm_gemm_bf16(const dwm_gemm_args* a_in, void* stream) {
     if (a_in == nullptr) return DWM_EINVAL;
     // tile == 3: "automatic, and the 4-wave kernels may serve the launch" (what the MMDiT inference forward asks for); 4: the same,
-    // their fast form only
+    // their fast form only.  The checks, the plan and the kernels see them as tile 0.
+    const int tile_asked = a_in->tile;
     dwm_gemm_args a_copy;
-    const bool allow4w = a_in->tile == 3 || a_in->tile == 4;
-    const bool fast_only4w = a_in->tile == 4;
-    if (allow4w) { a_copy = *a_in; a_copy.tile = 0; }
-    const dwm_gemm_args* a = allow4w ? &a_copy : a_in;
-    if (a == nullptr || a->A == nullptr || a->W == nullptr || (a->C == nullptr && a->C32 == nullptr)) return DWM_EINVAL;
-    if (a->M <= 0 || a->N <= 0 || a->K <= 0 || a->M >= (1ll << 31) || a->N >= (1ll << 31)) return DWM_EINVAL;
-    if (a->K % BK != 0 || a->N % 8 != 0) return DWM_EUNSUPPORTED;
-    if (a->lda % 8 != 0 || (a->C != nullptr && a->ldc % 8 != 0)) return DWM_EALIGN;
-    if (!dwm_aligned16(a->A) || !dwm_aligned16(a->W) || !dwm_aligned16(a->C)) return DWM_EALIGN;
-    if (a->bias && (((uintptr_t)a->bias) & 7u)) return DWM_EALIGN;
-    const int64_t nout = a->epilogue == DWM_EPI_GEGLU ? a->N / 2 : a->N;
-    if (a->C != nullptr && a->ldc < nout) return DWM_EINVAL;
-    switch (a->epilogue) {
-        case DWM_EPI_PLAIN: break;
-        case DWM_EPI_GEGLU:
-            if (a->N % 64 != 0 || (a->N / 2) % 8 != 0) return DWM_EUNSUPPORTED;
-            break;
-        case DWM_EPI_RESID:
-            if (a->gate && (a->rows_per_gate <= 0 || a->ld_gate % 8 != 0 || !dwm_aligned16(a->gate))) return DWM_EINVAL;
-            if (a->res && (a->ld_res % (a->C32 ? 4 : 8) != 0 || !dwm_aligned16(a->res))) return DWM_EALIGN;
-            if (a->blend && (a->alpha == nullptr || a->rows_per_alpha <= 0 || a->ld_blend % (a->C32 ? 4 : 8) != 0 || !dwm_aligned16(a->blend))) return DWM_EINVAL;
-            if (a->gate && a->blend) return DWM_EUNSUPPORTED;      // one register set carries the gate OR the blend rows
-            if (a->C32 != nullptr && ((a->res != nullptr && a->ld_res % 4 != 0) || a->ldc32 % 4 != 0 || a->ldc32 < a->N ||
-                                      !dwm_aligned16(a->C32) || a->res_mod != 0 || a->split_k > 1)) return DWM_EINVAL;
-            break;
-        case DWM_EPI_RMSHEAD:
-            if (a->rms_w == nullptr || a->rms_ncols % 64 != 0 || a->N % 64 != 0) return DWM_EINVAL;
-            break;
-        default: return DWM_EINVAL;
-    }
-    if (a->C32 != nullptr && a->epilogue != DWM_EPI_RESID) return DWM_EUNSUPPORTED;
-    {
-        // (kernel selection comes from the arguments only: the library reads no environment)
-        const bool use4w = allow4w;
-        if (use4w && !DWM_RESERVED(a->reserved) && a->lda % 64 == 0) {
-            const int rc4 = dwm_gemm4w_try(a, stream, fast_only4w);
-            if (rc4 >= 0) return rc4;
-        }
-    }
-    ConvParams cp;
-    if (!make_dev_rowmap(a->a_map, cp.a) || !make_dev_rowmap(a->c_map, cp.c)) return DWM_EINVAL;
-    const int ntaps = a->ntaps > 0 ? a->ntaps : 1;
-    if (ntaps > 27) return DWM_EINVAL;
-    const int64_t kpt = a->ntaps > 0 ? a->k_per_tap : a->K;
-    if (kpt <= 0 || kpt % BK != 0 || kpt * ntaps != a->K) return DWM_EINVAL;
-    if (a->rows_per_gate > (1ll << 30) || a->res_mod > (1ll << 30) || a->res_mod < -(1ll << 30) || a->rows_per_alpha > (1ll << 30)) return DWM_EINVAL;
-    set_dividers(cp, *a, kpt);
-    for (int t = 0; t < 27; ++t) cp.tap_shift[t] = (a->ntaps > 0 && t < ntaps) ? a->tap_shift[t] : 0;
-    if (a->lda < kpt) return DWM_EINVAL;
-    if (a->tile < 0 || a->tile > 2) return DWM_EINVAL;
-    int ntm = (int)((a->M + BM - 1) / BM), ntn = (int)((a->N + BN - 1) / BN);
-    set_raster(cp, *a, ntn);
+    if (tile_asked == 3 || tile_asked == 4) { a_copy = *a_in; a_copy.tile = 0; }
+    const dwm_gemm_args& a = tile_asked == 3 || tile_asked == 4 ? a_copy : *a_in;
+
+    if (a.A == nullptr || a.W == nullptr || (a.C == nullptr && a.C32 == nullptr)) return DWM_EINVAL;
+    int rc = check_sizes(a, kBf16);
+    if (rc != DWM_OK) return rc;
+    if (a.lda % 8 != 0 || (a.C != nullptr && a.ldc % 8 != 0)) return DWM_EALIGN;
+    if (!dwm_aligned16(a.A) || !dwm_aligned16(a.W) || !dwm_aligned16(a.C)) return DWM_EALIGN;
+    if (a.bias && (((uintptr_t)a.bias) & 7u)) return DWM_EALIGN;         // (known asymmetry: dwm_gemm_f32 does not look at it)
+    if (a.C != nullptr && a.ldc < gemm_nout(a)) return DWM_EINVAL;
+    rc = check_epilogue(a, kBf16);
+    if (rc != DWM_OK) return rc;
+    if (a.C32 != nullptr && a.epilogue != DWM_EPI_RESID) return DWM_EUNSUPPORTED;
+
+    // (kernel selection comes from the arguments only: the library reads no environment)
+    GemmPlan plan;
+    rc = plan_gemm(a, tile_asked, plan);
+    if (rc != DWM_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e;
-    // ---- split-K: a grid that fills less than half of the 256 CUs and a long K.  One K range per workgroup,
-    // fp32 partials in the caller's workspace, deterministic reduction + epilogue in splitk_finish_kernel.
-    int ksplit = 1;
-    {
-        const int64_t tiles = (int64_t)ntm * ntn, nk = a->K / BK;
-        const bool can = (a->epilogue == DWM_EPI_PLAIN || a->epilogue == DWM_EPI_RESID) && a->workspace != nullptr &&
-                         dwm_aligned16(a->workspace) && !(DWM_RESERVED(a->reserved) & 3) && a->C32 == nullptr;
-        if (a->split_k > 1) {
-            if (!can) return DWM_EUNSUPPORTED;
-            ksplit = a->split_k;
-        } else if (a->split_k == 0 && can && tiles <= 128 && nk >= 16) {
-            ksplit = (int)(256 / tiles);
-        }
-        if (ksplit > 1) {
-            const int64_t slice_bytes = a->M * a->N * 4;
-            if (ksplit > nk / 8) ksplit = (int)(nk / 8);
-            if (ksplit > 32) ksplit = 32;
-            if ((int64_t)ksplit * slice_bytes > a->workspace_bytes) ksplit = (int)(a->workspace_bytes / slice_bytes);
-            if (ksplit < 2) {
-                if (a->split_k > 1) return DWM_EUNSUPPORTED;
-                ksplit = 1;
-            }
-        }
+    if (plan.family == GemmFamily::W4_FAST || plan.family == GemmFamily::W4_GENERAL) return dwm_gemm4w_launch(a, plan, s);
+    ConvParams cp;
+    fill_conv_params(a, plan, cp);
+    switch (plan.family) {
+        case GemmFamily::W8_SPLITK: return launch_splitk(a, cp, plan, s);
+        case GemmFamily::W8_C32: return launch_c32(a, cp, plan, s);
+        default: return launch_tile(a, cp, plan, s);
     }
-    cp.ksplit = ksplit;
-    cp.ws = (float*)a->workspace;
-    cp.ws_slice = a->M * a->N;
-    if (ksplit > 1) {
-        e = dwm_allow_dynamic_lds<gemm_bf16_kernel<EPI_SPLITK>>(LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(gemm_bf16_kernel<EPI_SPLITK>, dim3((unsigned)(ntm * ntn * ksplit)), dim3(512), LDS_BYTES, s, *a, cp, ntm, ntn);
-        const int64_t nthr = a->M * (a->N >> 3);
-        hipLaunchKernelGGL(splitk_finish_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, *a, cp);
-        return dwm_launch_status();
-    }
-    // ---- tile configuration (TileCfg): 256 x 128 tiles (two workgroups per CU) on request, or automatically where they
-    // cut the padded columns (N = 320 -> 384 instead of 512: the SD 2.1 UNet's first level) AND K is short, i.e. the
-    // epilogue's share is large (measured, profiles/README.md: N = 320, K = 320: 1.17 x; with K >= 2880 the 256 x 256
-    // main loop wins although it pads more)
-    int tc = a->tile == 2 ? 1 : 0;
-    if (a->tile == 0 && a->C32 == nullptr) {
-        const int64_t c256 = (a->N + 255) / 256 * 256, c128 = (a->N + 127) / 128 * 128;
-        if (c128 < c256 && a->K <= 640) tc = 1;
-    }
-    if (DWM_RESERVED(a->reserved) & 0x200) tc = 1;
-    if (tc == 1 && a->C32 != nullptr) return DWM_EUNSUPPORTED;
-    if (tc == 1) {
-        ntn = (int)((a->N + TileCfg<1>::bn - 1) / TileCfg<1>::bn);
-        cp.steps_per_tap = (int)(kpt / TileCfg<1>::bk);
-        cp.fd_steps = make_fastdiv((uint32_t)cp.steps_per_tap);
-        set_raster(cp, *a, ntn);
-    }
-    const dim3 grid((unsigned)(ntm * ntn)), block(tc == 1 ? TileCfg<1>::nwaves * 64 : 512);
-#define DWM_LAUNCH_TC(EPI, FAST, TC_)                                                                \
-    do {                                                                                             \
-        e = dwm_allow_dynamic_lds<gemm_bf16_kernel<EPI, FAST, false, TC_>>(tile_lds_bytes<TC_>() + (TC_ ? DWM_DEV_LDS_PAD : 0)); \
-        if (e != hipSuccess) return (int)e;                                                          \
-        hipLaunchKernelGGL((gemm_bf16_kernel<EPI, FAST, false, TC_>), grid, block,                   \
-                           tile_lds_bytes<TC_>() + ((TC_ && (DWM_RESERVED(a->reserved) & 0x400)) ? DWM_DEV_LDS_PAD : 0), s, *a, cp, ntm, ntn); \
-    } while (0)
-#define DWM_LAUNCH(EPI, FAST)                                                                        \
-    do {                                                                                             \
-        if (tc == 1) DWM_LAUNCH_TC(EPI, FAST, 1); else DWM_LAUNCH_TC(EPI, FAST, 0);                  \
-    } while (0)
-    // the transformer blocks' linear layers (see FAST above); reserved bit 2 keeps the general kernels (A/B measurements)
-    const int64_t lim = 1ll << 31;
-    bool fast = !cp.c.enabled && a->ldc < lim && !(DWM_RESERVED(a->reserved) & 4);
-    const int rs16 = (a->gate ? 1 : 0) | (a->res ? 2 : 0) | (a->blend ? 4 : 0) | ((a->res && a->res_mod < 0) ? 16 : 0);
-    if (a->epilogue == DWM_EPI_RESID)
-        fast = fast && (a->res_mod == 0 || (rs16 == 18 && a->C32 == nullptr)) && a->act == DWM_ACT_NONE &&
-               (a->gate == nullptr || a->ld_gate < lim) && (a->res == nullptr || a->ld_res < lim) && (a->blend == nullptr || a->ld_blend < lim);
-#define DWM_LAUNCH2(EPI)                                                                             \
-    do {                                                                                             \
-        if (fast) DWM_LAUNCH(EPI, true); else DWM_LAUNCH(EPI, false);                                \
-    } while (0)
-    if (a->C32 != nullptr) {                 // fp32 residual stream: RESID with fp32 residual / blend rows and fp32 output
-        e = dwm_allow_dynamic_lds<gemm_bf16_kernel<DWM_EPI_RESID, false, true>>(LDS_BYTES);
-        if (e == hipSuccess) e = dwm_allow_dynamic_lds<gemm_bf16_kernel<DWM_EPI_RESID, true, true>>(LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        // the transformer blocks' hidden-state stream takes the FAST form (32-bit row arithmetic, no row map, no activation), and
-        // its three operand sets - gate + residual, residual, residual + blend, no bf16 mirror - their compile-time forms (RS)
-        const int rs = (a->gate ? 1 : 0) | (a->res ? 2 : 0) | (a->blend ? 4 : 0) | (a->C ? 8 : 0);
-#define DWM_LAUNCH_RS(RS_)                                                                                        \
-        do {                                                                                                      \
-            e = dwm_allow_dynamic_lds<gemm_bf16_kernel<DWM_EPI_RESID, true, true, 0, RS_>>(LDS_BYTES);            \
-            if (e != hipSuccess) return (int)e;                                                                   \
-            hipLaunchKernelGGL((gemm_bf16_kernel<DWM_EPI_RESID, true, true, 0, RS_>), grid, block, LDS_BYTES, s, *a, cp, ntm, ntn); \
-        } while (0)
-        if (fast && a->ldc32 < lim) {
-            if (rs == 3) DWM_LAUNCH_RS(3);
-            else if (rs == 2) DWM_LAUNCH_RS(2);
-            else if (rs == 6) DWM_LAUNCH_RS(6);
-            else hipLaunchKernelGGL((gemm_bf16_kernel<DWM_EPI_RESID, true, true>), grid, block, LDS_BYTES, s, *a, cp, ntm, ntn);
-        } else {
-            hipLaunchKernelGGL((gemm_bf16_kernel<DWM_EPI_RESID, false, true>), grid, block, LDS_BYTES, s, *a, cp, ntm, ntn);
-        }
-#undef DWM_LAUNCH_RS
-        return dwm_launch_status();
-    }
-    // bf16 RESID, FAST form: the operand sets of the transformer blocks at compile time as well (RS: gate + residual, residual,
-    // residual + blend) - the SD 2.1 UNet's K = 320 ... 1280 GEMMs are mostly epilogue
-#define DWM_LAUNCH_RS16(TC_, RS_)                                                                                 \
-    do {                                                                                                          \
-        e = dwm_allow_dynamic_lds<gemm_bf16_kernel<DWM_EPI_RESID, true, false, TC_, RS_>>(tile_lds_bytes<TC_>() + (TC_ ? DWM_DEV_LDS_PAD : 0)); \
-        if (e != hipSuccess) return (int)e;                                                                       \
-        hipLaunchKernelGGL((gemm_bf16_kernel<DWM_EPI_RESID, true, false, TC_, RS_>), grid, block,                 \
-                           tile_lds_bytes<TC_>() + ((TC_ && (DWM_RESERVED(a->reserved) & 0x400)) ? DWM_DEV_LDS_PAD : 0), s, *a, cp, ntm, ntn); \
-    } while (0)
-    const bool spec16 = a->epilogue == DWM_EPI_RESID && fast && (rs16 == 2 || rs16 == 3 || rs16 == 6 || rs16 == 18);
-    if (spec16) {
-        if (tc == 1) {
-            if (rs16 == 2) DWM_LAUNCH_RS16(1, 2); else if (rs16 == 3) DWM_LAUNCH_RS16(1, 3); else if (rs16 == 6) DWM_LAUNCH_RS16(1, 6);
-            else DWM_LAUNCH_RS16(1, 18);
-        } else {
-            if (rs16 == 2) DWM_LAUNCH_RS16(0, 2); else if (rs16 == 3) DWM_LAUNCH_RS16(0, 3); else if (rs16 == 6) DWM_LAUNCH_RS16(0, 6);
-            else DWM_LAUNCH_RS16(0, 18);
-        }
-    } else
-    switch (a->epilogue) {
-        case DWM_EPI_PLAIN: DWM_LAUNCH2(DWM_EPI_PLAIN); break;
-        case DWM_EPI_GEGLU: DWM_LAUNCH2(DWM_EPI_GEGLU); break;
-        case DWM_EPI_RESID: DWM_LAUNCH2(DWM_EPI_RESID); break;
-        default: DWM_LAUNCH2(DWM_EPI_RMSHEAD); break;
-    }
-#undef DWM_LAUNCH_RS16
-#undef DWM_LAUNCH2
-#undef DWM_LAUNCH
-#undef DWM_LAUNCH_TC
-    return dwm_launch_status();
 }

@@ -23,13 +23,14 @@
 // gate / residual / blend rows and the stores.  RESID comes in the compile-time operand forms (RS) only: residual, gate + residual,
 // residual + blend, on the fp32 stream (RF32, no bf16 copy) or in bf16.
 // Covered launches (everything else stays on gemm_bf16.hip): no row maps, no taps, no split-K, M % 256 == N % 256 == K % 64 == 0.
-// General form (template parameter GEN): ragged M / N, the A row map, taps, the per-image residual row - see dwm_gemm4w_try.
+// General form (template parameter GEN): ragged M / N, the A row map, taps, the per-image residual row - see dwm_gemm4w_covers.
 #include <atomic>
 
-#include "common.h"
-#include "dwm_hip.h"
+#include "gemm_common.h"
 
 namespace {
+
+using namespace dwm_gemm;
 
 typedef __attribute__((ext_vector_type(8))) __bf16 hbf16x8;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
@@ -41,30 +42,19 @@ constexpr int W_BASE = AST * TILE;
 constexpr int LDS_BYTES = (AST + WST) * TILE;     // 160 KiB
 constexpr int NJ = TILE / (4 * 1024);             // 1-KiB requests per wave, operand and stage: 8
 
-struct G4Map {              // dwm_rowmap2d with fast divisors (gemm_bf16.hip's DevRowMap)
-    FastDiv rw, rh;
-    int64_t rpitch, ipitch, origin;
-    int enabled, xstep;
-};
 struct G4Params {
     int ntm, ntn, gm;
     FastDiv fd_rpg, fd_rpa;
     // general form (GEN): the A row map, the taps of an implicit convolution as byte offsets from the row of the smallest shift
     // (the A resource starts `a_base_rows` rows from p.A, so every offset is >= 0), the divisor of the per-image residual row
     FastDiv fd_rmod;
-    G4Map amap;
+    DevRowMap amap;
     int steps_per_tap;
     int64_t a_base_rows;
     uint32_t tap_off[27];
 };
-DWM_DEVINL int64_t map_row4(const G4Map& rm, int64_t m) {
-    if (!rm.enabled) return m;
-    const uint32_t q = fdiv((uint32_t)m, rm.rw), x = (uint32_t)m - q * rm.rw.d;
-    const uint32_t i = fdiv(q, rm.rh), y = q - i * rm.rh.d;
-    return (int64_t)i * rm.ipitch + (int64_t)y * rm.rpitch + (int64_t)x * rm.xstep + rm.origin;
-}
 
-// GEN (general form, see dwm_gemm4w_try): ragged M / N (operand rows clamped to the last one, stores guarded), A rows through
+// GEN (general form, see dwm_gemm4w_covers): ragged M / N (operand rows clamped to the last one, stores guarded), A rows through
 // the row map `a_map`, K walked tap by tap (implicit convolution), RS bit 16 (the residual row is m / |res_mod|).  The per-lane
 // request offsets then differ from request to request (one VGPR each instead of two per operand) and the K walk of A is a scalar
 // that jumps at tap boundaries (the table sits in a VGPR, one lane per tap, read by v_readlane: gemm_bf16.hip's reason).
@@ -121,7 +111,7 @@ gemm4w_kernel(const dwm_gemm_args p, const G4Params gp) {
             const uint32_t ch = (uint32_t)((lane & 7) ^ ((row >> 1) & 7)) * 16u;
             int64_t gmr = m0 + row; gmr = gmr < M ? gmr : M - 1;
             int64_t gnr = n0 + row; gnr = gnr < N ? gnr : N - 1;
-            va[j] = (uint32_t)map_row4(gp.amap, gmr) * (uint32_t)(p.lda * 2) + ch;
+            va[j] = (uint32_t)map_row(gp.amap, gmr) * (uint32_t)(p.lda * 2) + ch;
             vw[j] = (uint32_t)gnr * (uint32_t)(K * 2) + ch;
         }
         // (the tap table's load is consumed HERE, before the first request: its wait behind them would drain them)
@@ -467,112 +457,130 @@ std::atomic<int64_t> g_launches{0};
 std::atomic<int64_t> g_launches_gen{0};
 
 template <int EPI, bool RF32, int RS, bool GEN = false>
-int launch4w(const dwm_gemm_args* a, const G4Params& gp, hipStream_t s) {
+int launch4w(const dwm_gemm_args& a, const G4Params& gp, hipStream_t s) {
     const hipError_t e = dwm_allow_dynamic_lds<gemm4w_kernel<EPI, RF32, RS, GEN>>(LDS_BYTES);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((gemm4w_kernel<EPI, RF32, RS, GEN>), dim3((unsigned)(gp.ntm * gp.ntn)), dim3(256), LDS_BYTES, s, *a, gp);
+    hipLaunchKernelGGL((gemm4w_kernel<EPI, RF32, RS, GEN>), dim3((unsigned)(gp.ntm * gp.ntn)), dim3(256), LDS_BYTES, s, a, gp);
     g_launches.fetch_add(1, std::memory_order_relaxed);
     if (GEN) g_launches_gen.fetch_add(1, std::memory_order_relaxed);
     return dwm_launch_status();
 }
+template <int EPI, bool RF32, int RS>
+int launch4w_form(const dwm_gemm_args& a, const G4Params& gp, bool gen, hipStream_t s) {
+    return gen ? launch4w<EPI, RF32, RS, true>(a, gp, s) : launch4w<EPI, RF32, RS, false>(a, gp, s);
+}
+
+// smallest / largest tap shift, in rows (0 / 0 without taps)
+void tap_span(const dwm_gemm_args& a, int64_t& smin, int64_t& smax) {
+    smin = smax = 0;
+    for (int t = 0; t < a.ntaps; ++t) {
+        smin = a.tap_shift[t] < smin ? a.tap_shift[t] : smin;
+        smax = a.tap_shift[t] > smax ? a.tap_shift[t] : smax;
+    }
+}
+
+// the kernel's parameter block for a launch dwm_gemm4w_covers accepted
+void fill_g4(const dwm_gemm_args& a, const GemmPlan& plan, G4Params& gp) {
+    gp.ntm = plan.ntm; gp.ntn = plan.ntn;
+    gp.gm = plan.gm;
+    gp.fd_rpg = make_fastdiv((uint32_t)(a.rows_per_gate > 0 ? a.rows_per_gate : 1));
+    gp.fd_rpa = make_fastdiv((uint32_t)(a.rows_per_alpha > 0 ? a.rows_per_alpha : 1));
+    gp.fd_rmod = make_fastdiv((uint32_t)(a.res_mod < 0 ? -a.res_mod : 1));
+    const dwm_rowmap2d identity = {};
+    make_dev_rowmap(a.a_map.rw > 0 ? a.a_map : identity, gp.amap);
+    gp.steps_per_tap = (int)(a.K / BK);
+    gp.a_base_rows = 0;
+    for (int t = 0; t < 27; ++t) gp.tap_off[t] = 0;
+    if (plan.family != GemmFamily::W4_GENERAL) return;
+    // general form: the taps as byte offsets from the row of the smallest shift
+    gp.steps_per_tap = (int)(gemm_k_per_tap(a) / BK);
+    int64_t smin, smax;
+    tap_span(a, smin, smax);
+    gp.a_base_rows = smin;
+    for (int t = 0; t < a.ntaps; ++t) gp.tap_off[t] = (uint32_t)((a.tap_shift[t] - smin) * a.lda * 2);
+}
 
 }  // namespace
 
-// Called by dwm_gemm_bf16 (gemm_bf16.hip) after its argument validation when the caller (tile == 3) or DWM_GEMM4W asks for it.
-// Returns -1 if this launch is not one the 4-wave kernels cover (the caller then continues with the 8-wave kernels), otherwise the
-// launch status.
-//   fast form: no row maps, no taps, no split-K, M % 256 == N % 256 == K % 64 == 0.
+// Whether the 4-wave kernels serve a launch that passed the argument checks of dwm_gemm_bf16 up to its epilogue operands (plan_gemm in
+// gemm_bf16.hip asks for tile == 3 / 4 only; tile 1 / 2 name an 8-wave configuration and never come here).
+//   never: an OUTPUT row map, split-K - asked for, or what the automatic rule would take (auto_splitk; see there where this
+//   answer and the 8-wave planner's part) -, one K step (K < 128: a known bad corner of the request form), a leading dimension of
+//   an epilogue operand >= 2^31, RESID with res_mod > 0, an activation, no residual or operands other than residual / gate +
+//   residual / residual + blend, C32 together with a bf16 mirror or with the per-image residual row.
+//   fast form: no A row map, no taps, M % 256 == N % 256 == 0, res_mod == 0; request offsets within 32 bits.
 //   general form (GEN; validated on the GPU in round 5, profiles/r5a_*: 22-call battery against fp64 / conv2d and the 8-wave kernels,
-//   393.8 -> 389.4 ms per denoise step on one box): ragged M / N (N % 8 == 0; GEGLU / RMSHEAD: N % 64 == 0), an A row map, taps
-//   (implicit convolution), the per-image residual row (res_mod < 0) - no OUTPUT row map, no split-K.
-int dwm_gemm4w_try(const dwm_gemm_args* a, void* stream, bool fast_only) {
-    // fast_only (dwm_gemm_args.tile == 4): the fast form only (A/B measurements of the general form)
+//   393.8 -> 389.4 ms per denoise step on one box), not with fast_only: ragged M / N, an A row map, taps (implicit convolution),
+//   the per-image residual row (res_mod < 0; bf16 residual + nothing else: RS 18 exists in this form only).  Everything
+//   dwm_gemm_bf16 rejects after this point is DECLINED here, not rejected: the 8-wave path then returns its error code.
+bool dwm_gemm4w_covers(const dwm_gemm_args& a, bool fast_only, GemmPlan& plan) {
     const int64_t lim = 1ll << 31;
-    if (a->c_map.rw > 0 || a->split_k > 1 || a->tile == 1 || a->tile == 2) return -1;        // (tile 1 / 2: an 8-wave configuration was asked for)
-    if (a->K % BK != 0 || a->K < 2 * BK) return -1;        // (one K step: a known bad corner of the request form)
-    const bool row_div = a->epilogue == DWM_EPI_RESID && a->res_mod < 0;
-    const bool gen = a->a_map.rw > 0 || a->ntaps > 0 || a->M % BM != 0 || a->N % BN != 0 || row_div;
-    if (gen && fast_only) return -1;
-    if (a->ldc >= lim || a->ldc32 >= lim || a->ld_res >= lim || a->ld_blend >= lim || a->ld_gate >= lim) return -1;
-    // the automatic split-K rule of dwm_gemm_bf16 (small tile grids with a long K) keeps its kernels
-    const int ntm = (int)((a->M + BM - 1) / BM), ntn = (int)((a->N + BN - 1) / BN);
-    if ((a->epilogue == DWM_EPI_PLAIN || a->epilogue == DWM_EPI_RESID) && a->workspace != nullptr && a->split_k == 0 &&
-        (int64_t)ntm * ntn <= 128 && a->K / BK >= 16 && a->C32 == nullptr)
-        return -1;
-    G4Params gp;
-    gp.ntm = ntm; gp.ntn = ntn;
-    gp.gm = a->K >= 4096 ? 4 : 8;
-    gp.fd_rpg = make_fastdiv((uint32_t)(a->rows_per_gate > 0 ? a->rows_per_gate : 1));
-    gp.fd_rpa = make_fastdiv((uint32_t)(a->rows_per_alpha > 0 ? a->rows_per_alpha : 1));
-    gp.fd_rmod = make_fastdiv((uint32_t)(a->res_mod < 0 ? -a->res_mod : 1));
-    gp.amap.enabled = 0; gp.amap.xstep = 1; gp.amap.rw = gp.amap.rh = make_fastdiv(1); gp.amap.rpitch = gp.amap.ipitch = gp.amap.origin = 0;
-    gp.steps_per_tap = (int)(a->K / BK);
-    gp.a_base_rows = 0;
-    for (int t = 0; t < 27; ++t) gp.tap_off[t] = 0;
+    if (a.c_map.rw > 0 || a.split_k > 1 || a.K < 2 * BK) return false;
+    const bool row_div = a.epilogue == DWM_EPI_RESID && a.res_mod < 0;
+    const bool gen = a.a_map.rw > 0 || a.ntaps > 0 || a.M % BM != 0 || a.N % BN != 0 || row_div;
+    if (gen && fast_only) return false;
+    if (a.ldc >= lim || a.ldc32 >= lim || a.ld_res >= lim || a.ld_blend >= lim || a.ld_gate >= lim) return false;
+    const int ntm = (int)((a.M + BM - 1) / BM), ntn = (int)((a.N + BN - 1) / BN);
+    if (auto_splitk(a, (int64_t)ntm * ntn)) return false;
+    int rs = 0;
+    if (a.epilogue == DWM_EPI_RESID) {
+        if (a.res_mod > 0 || a.act != DWM_ACT_NONE || a.res == nullptr) return false;
+        rs = (a.gate ? 1 : 0) | 2 | (a.blend ? 4 : 0) | (row_div ? 16 : 0);
+        if (a.C32 != nullptr && (a.C != nullptr || row_div)) return false;        // (the form with the bf16 copy stays on the 8-wave kernel)
+        if (rs != 2 && rs != 3 && rs != 6 && !(rs == 18 && a.C32 == nullptr)) return false;
+    } else if (a.C32 != nullptr) {
+        return false;
+    }
     if (!gen) {
-        if (a->lda * 2 * BM >= lim || a->K * 2 * BN >= lim || a->lda * 2 >= (1ll << 28)) return -1;            // 32-bit request offsets
+        if (a.lda * 2 * BM >= lim || a.K * 2 * BN >= lim || a.lda * 2 >= (1ll << 28)) return false;            // 32-bit request offsets
     } else {
-        // anything gemm_bf16.hip would reject is left to it (its error codes)
-        if (a->M <= 0 || a->N <= 0 || a->N % 8 != 0) return -1;
-        if ((a->epilogue == DWM_EPI_GEGLU || a->epilogue == DWM_EPI_RMSHEAD) && a->N % 64 != 0) return -1;
-        if (a->M >= (1ll << 30) || a->res_mod < -(1ll << 30) || a->rows_per_gate > (1ll << 30) || a->rows_per_alpha > (1ll << 30)) return -1;
-        const int ntaps = a->ntaps > 0 ? a->ntaps : 1;
-        const int64_t kpt = a->ntaps > 0 ? a->k_per_tap : a->K;
-        if (ntaps > 27 || kpt <= 0 || kpt % BK != 0 || kpt * ntaps != a->K || a->lda < kpt) return -1;
-        gp.steps_per_tap = (int)(kpt / BK);
-        if (a->a_map.rw > 0) {
-            const dwm_rowmap2d& r = a->a_map;
-            if (r.rh <= 0 || r.rw >= (1ll << 30) || r.rh >= (1ll << 30)) return -1;
-            gp.amap.enabled = 1;
-            gp.amap.xstep = r.xstep > 0 ? (int)r.xstep : 1;
-            gp.amap.rw = make_fastdiv((uint32_t)r.rw); gp.amap.rh = make_fastdiv((uint32_t)r.rh);
-            gp.amap.rpitch = r.rpitch; gp.amap.ipitch = r.ipitch; gp.amap.origin = r.origin;
-        }
+        if (a.M >= (1ll << 30) || a.res_mod < -(1ll << 30) || a.rows_per_gate > (1ll << 30) || a.rows_per_alpha > (1ll << 30)) return false;
+        const int ntaps = gemm_ntaps(a);
+        const int64_t kpt = gemm_k_per_tap(a);
+        if (ntaps > 27 || kpt <= 0 || kpt % BK != 0 || kpt * ntaps != a.K || a.lda < kpt) return false;
+        DevRowMap amap;
+        if (!make_dev_rowmap(a.a_map, amap)) return false;
         // rows of A the launch reaches, counted from the row of the smallest tap shift: every 32-bit offset must stay below 2^31
-        int64_t smin = 0, smax = 0;
-        for (int t = 0; t < ntaps && a->ntaps > 0; ++t) {
-            smin = a->tap_shift[t] < smin ? a->tap_shift[t] : smin;
-            smax = a->tap_shift[t] > smax ? a->tap_shift[t] : smax;
-        }
-        int64_t last = a->M - 1;                             // the map is monotone: its largest row is the last pixel's
-        if (a->a_map.rw > 0) {
-            const dwm_rowmap2d& r = a->a_map;
+        int64_t smin, smax;
+        tap_span(a, smin, smax);
+        int64_t last = a.M - 1;                              // the map is monotone: its largest row is the last pixel's
+        if (a.a_map.rw > 0) {
+            const dwm_rowmap2d& r = a.a_map;
             const int64_t q = last / r.rw, x = last % r.rw, img = q / r.rh, y = q % r.rh;
             last = img * r.ipitch + y * r.rpitch + x * (r.xstep > 0 ? r.xstep : 1) + r.origin;
         }
-        if (last < 0 || (last + smax - smin + 1) * a->lda * 2 + a->K * 2 >= lim || a->N * a->K * 2 >= lim) return -1;
-        gp.a_base_rows = smin;
-        for (int t = 0; t < ntaps && a->ntaps > 0; ++t) gp.tap_off[t] = (uint32_t)((a->tap_shift[t] - smin) * a->lda * 2);
+        if (last < 0 || (last + smax - smin + 1) * a.lda * 2 + a.K * 2 >= lim || a.N * a.K * 2 >= lim) return false;
     }
-    hipStream_t s = (hipStream_t)stream;
-#define DWM4_GO(...) return gen ? launch4w<__VA_ARGS__, true>(a, gp, s) : launch4w<__VA_ARGS__, false>(a, gp, s)
-    switch (a->epilogue) {
-        case DWM_EPI_PLAIN:
-            if (a->C32 != nullptr) return -1;
-            DWM4_GO(DWM_EPI_PLAIN, false, 0);
-        case DWM_EPI_GEGLU:
-            DWM4_GO(DWM_EPI_GEGLU, false, 0);
-        case DWM_EPI_RMSHEAD:
-            DWM4_GO(DWM_EPI_RMSHEAD, false, 0);
-        case DWM_EPI_RESID: {
-            if (a->res_mod > 0 || a->act != DWM_ACT_NONE || a->res == nullptr) return -1;
-            const int rs = (a->gate ? 1 : 0) | 2 | (a->blend ? 4 : 0) | (row_div ? 16 : 0);
-            if (a->C32 != nullptr) {
-                if (a->C != nullptr || row_div) return -1;        // (the form with the bf16 copy stays on the 8-wave kernel)
-                if (rs == 2) DWM4_GO(DWM_EPI_RESID, true, 2);
-                if (rs == 3) DWM4_GO(DWM_EPI_RESID, true, 3);
-                if (rs == 6) DWM4_GO(DWM_EPI_RESID, true, 6);
-                return -1;
-            }
-            if (rs == 2) DWM4_GO(DWM_EPI_RESID, false, 2);
-            if (rs == 3) DWM4_GO(DWM_EPI_RESID, false, 3);
-            if (rs == 6) DWM4_GO(DWM_EPI_RESID, false, 6);
-            if (rs == 18) return launch4w<DWM_EPI_RESID, false, 18, true>(a, gp, s);
-            return -1;
-        }
-        default: return -1;
+    plan.family = gen ? GemmFamily::W4_GENERAL : GemmFamily::W4_FAST;
+    plan.epi = a.epilogue; plan.rs = rs;
+    plan.fast = !gen; plan.rf32 = a.C32 != nullptr;
+    plan.tc = 0;
+    plan.ntm = ntm; plan.ntn = ntn;
+    plan.grid = (unsigned)(ntm * ntn); plan.block = 256; plan.lds = LDS_BYTES;
+    plan.ksplit = 1;
+    plan.gm = raster_group_height(a.K);
+    return true;
+}
+
+int dwm_gemm4w_launch(const dwm_gemm_args& a, const GemmPlan& plan, hipStream_t s) {
+    G4Params gp;
+    fill_g4(a, plan, gp);
+    const bool gen = plan.family == GemmFamily::W4_GENERAL;
+    switch (plan.epi) {
+        case DWM_EPI_PLAIN: return launch4w_form<DWM_EPI_PLAIN, false, 0>(a, gp, gen, s);
+        case DWM_EPI_GEGLU: return launch4w_form<DWM_EPI_GEGLU, false, 0>(a, gp, gen, s);
+        case DWM_EPI_RMSHEAD: return launch4w_form<DWM_EPI_RMSHEAD, false, 0>(a, gp, gen, s);
+        default: break;
     }
-#undef DWM4_GO
+    if (plan.rf32) {
+        if (plan.rs == 2) return launch4w_form<DWM_EPI_RESID, true, 2>(a, gp, gen, s);
+        if (plan.rs == 3) return launch4w_form<DWM_EPI_RESID, true, 3>(a, gp, gen, s);
+        return launch4w_form<DWM_EPI_RESID, true, 6>(a, gp, gen, s);
+    }
+    if (plan.rs == 2) return launch4w_form<DWM_EPI_RESID, false, 2>(a, gp, gen, s);
+    if (plan.rs == 3) return launch4w_form<DWM_EPI_RESID, false, 3>(a, gp, gen, s);
+    if (plan.rs == 6) return launch4w_form<DWM_EPI_RESID, false, 6>(a, gp, gen, s);
+    return launch4w<DWM_EPI_RESID, false, 18, true>(a, gp, s);
 }
 
 extern "C" int64_t dwm_gemm4w_launches(void) { return g_launches.load(std::memory_order_relaxed); }

@@ -2,9 +2,9 @@
 without a GPU at hand, DWM_GEMM4W=2): the index arithmetic that form adds to the validated kernel - restated in numpy, line by
 line, and held against a direct evaluation of the implicit convolution / ragged product:
 
-  * dwm_gemm4w_try (host): the A resource starts `a_base_rows` = the smallest tap shift before p.A, `tap_off[t]` = (shift_t -
+  * fill_g4 (host): the A resource starts `a_base_rows` = the smallest tap shift before p.A, `tap_off[t]` = (shift_t -
     smallest) * row pitch in bytes, `steps_per_tap` = k_per_tap / 64;
-  * the kernel: per request row `va = u32(map_row4(min(m0 + row, M - 1))) * u32(lda * 2)`, `vw = u32(min(n0 + row, N - 1)) *
+  * the kernel: per request row `va = u32(map_row(min(m0 + row, M - 1))) * u32(lda * 2)`, `vw = u32(min(n0 + row, N - 1)) *
     u32(K * 2)`; the scalar K walk of A (`walk_next`: + 128 bytes inside a tap, the next tap's offset at a boundary); W walks
     kt * 128 bytes; stores guarded by m < M, n < N.
 The arguments are the ones the product passes (ops.PaddedGrid / ops.TimeGrid fill the row map and the tap shifts).  What this does
