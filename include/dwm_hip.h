@@ -39,7 +39,7 @@ extern "C" {
 #define DWM_EUNSUPPORTED (-3)
 
 /* ABI version; bump on any struct change. */
-#define DWM_ABI_VERSION 17
+#define DWM_ABI_VERSION 18
 int dwm_abi_version(void);
 /* SHA-256 (hex) of the sources this library was built from (csrc .hip and .h files + this header, in sorted order), as
  * computed by opendwm_amd/build.py; the Python binding compares it with the sources it finds next to itself and refuses a
@@ -536,6 +536,36 @@ typedef struct dwm_adamw_item {
 int dwm_adamw_multi(const dwm_adamw_item* items, const int32_t* block_item, const int64_t* block_start, int64_t n_blocks,
                     int64_t chunk, float lr, float beta1, float beta2, float eps, float weight_decay, float bias_corr1,
                     float bias_corr2, float grad_scale, void* stream);
+
+/* Block-wise 8-bit optimizer state (the slot the reference's docs/CtsdPipelineFaqs.md, "Single GPU training", step 2, fills
+ * with bitsandbytes.optim.Adam8bit; the format follows "8-bit Optimizers via Block-wise Quantization", Dettmers et al. 2022).
+ *   - A tensor is cut into blocks of 256 consecutive elements (the last one may be partial).  Element i is stored as one byte
+ *     q[i] plus one fp32 scale per block: value = code[q[i]] * absmax[i / 256].
+ *   - `code` is a DEVICE table of 256 strictly increasing floats that contains 0 and 1 and whose minimum is >= -1, chosen
+ *     by the caller (opendwm_amd.quant8.dynamic_code: a signed table for the first moment, an unsigned one for the second);
+ *     no table is compiled into a kernel.
+ *   - Encoding a block: absmax = max |x|; y = x / absmax (a true fp32 division; absmax == 0: y = 0 and the scale 0 is
+ *     stored); q = the number of the 255 midpoints (code[k] + code[k + 1]) * 0.5f that are strictly less than y - the nearest
+ *     entry, ties going down.
+ *   - Guard (floor_positive, always on for the second moment of dwm_adamw8_multi): a strictly positive value never gets the
+ *     code of 0.0 but the smallest positive entry.  Otherwise an element whose gradient is tiny next to the largest of its
+ *     block would lose v while keeping m, and take a step of lr * m / eps the next time its gradient is exactly zero.
+ * n elements need n bytes of q and ceil(n / 256) floats of absmax.  Pointers need no alignment (16-byte aligned x, 4-byte
+ * aligned q take the vector path). */
+int dwm_quantize_blockwise8(const float* x, int64_t n, const float* code, int32_t floor_positive, uint8_t* q, float* absmax,
+                            void* stream);
+int dwm_dequantize_blockwise8(const uint8_t* q, const float* absmax, int64_t n, const float* code, float* x, void* stream);
+
+/* dwm_adamw_multi with both moments kept in the format above: decode m / v, g *= grad_scale, the same decoupled weight decay
+ * and update as dwm_adamw from the fresh fp32 moments, p and the bf16 copy written, m / v re-encoded (code_m for m, code_v with
+ * the guard for v) - one pass, 18 bytes per parameter instead of 30.  block_item / block_start / chunk as for dwm_adamw_multi,
+ * chunk a multiple of 256.  Deterministic: every block is reduced and written by one wave. */
+typedef struct dwm_adamw8_item {
+    float* p; const float* g; uint8_t* m_q; float* m_absmax; uint8_t* v_q; float* v_absmax; void* p_bf16; int64_t n;
+} dwm_adamw8_item;
+int dwm_adamw8_multi(const dwm_adamw8_item* items, const int32_t* block_item, const int64_t* block_start, int64_t n_blocks,
+                     int64_t chunk, const float* code_m, const float* code_v, float lr, float beta1, float beta2, float eps,
+                     float weight_decay, float bias_corr1, float bias_corr2, float grad_scale, void* stream);
 
 /* Backward of dwm_groupnorm_silu / dwm_groupnorm_silu_mapped (the UNet's ResnetBlock2D / TemporalResnetBlock / TransformerModel
  * norms in the SD 2.1 training branch, src/dwm/pipelines/ctsd.py:1240-1253): x = the forward input (compact rows, through

@@ -7,7 +7,7 @@ import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DWM_HIP_LIB") or os.path.join(HERE, "libdwm_hip.so")      # DWM_HIP_LIB: another build of the same ABI (A/B measurements)
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 EPI_PLAIN, EPI_GEGLU, EPI_RESID, EPI_RMSHEAD = 0, 1, 2, 3
 ACT_NONE, ACT_GELU_TANH, ACT_SILU, ACT_RELU = 0, 1, 2, 3
@@ -112,6 +112,10 @@ class LayerNormBwdArgs(C.Structure):
     ]
 
 
+class AdamW8Item(C.Structure):          # one row of the device array train_ops.adamw8_multi_ builds (8 x 8 bytes)
+    _fields_ = [("p", _vp), ("g", _vp), ("m_q", _vp), ("m_absmax", _vp), ("v_q", _vp), ("v_absmax", _vp), ("p_bf16", _vp), ("n", _i64)]
+
+
 # name -> (restype, argtypes); every symbol include/dwm_hip.h declares
 SIGNATURES = {
     "dwm_abi_version": (_i32, []),
@@ -185,6 +189,9 @@ SIGNATURES = {
     "dwm_rmsnorm_heads_bwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     "dwm_adamw": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp]),
     "dwm_adamw_multi": (_i32, [_vp, _vp, _vp, _i64, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp]),
+    "dwm_quantize_blockwise8": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _vp]),
+    "dwm_dequantize_blockwise8": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "dwm_adamw8_multi": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp]),
     "dwm_block_permute": (_i32, [C.POINTER(BlockPermuteArgs), _vp]),
     "dwm_cast_bf16_to_f32": (_i32, [_vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp]),
     "dwm_groupnorm_bwd": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _f32, _vp, _vp, _i32, _i32, _vp, _vp, _vp,

@@ -479,6 +479,189 @@ adamw_multi_kernel(const dwm_adamw_item* __restrict__ items, const int32_t* __re
     }
 }
 
+// ---------------------------------------------------------------------------------- block-wise 8-bit optimizer state
+// Format (include/dwm_hip.h, "Block-wise 8-bit optimizer state"): a value is code[q] * absmax[block], blocks of 256 consecutive
+// elements of one tensor, `code` a table of 256 increasing floats handed in by the caller.  One wave owns one block: lane l holds
+// elements 4 l .. 4 l + 3, so the four codes of a lane are one 32-bit word, fp32 data one 16-byte access, the bf16 shadow one
+// 8-byte store, and the block maximum is a cross-lane reduction of the wave (no LDS barrier, no atomics).  The tables and their
+// 255 midpoints sit in LDS: decoding is one gather, encoding an 8-step search over the midpoints.
+constexpr int Q8_BLOCK = 256;
+
+// table t -> LDS: tab[0..255] = code, tab[256..510] = midpoints of adjacent entries (tab[511] is never read).  All 256 threads.
+DWM_DEVINL void q8_stage_table(const float* __restrict__ code, float* tab) {
+    const int t = threadIdx.x;
+    tab[t] = code[t];
+    tab[256 + t] = t < 255 ? (code[t] + code[t + 1]) * 0.5f : 0.f;
+}
+
+// number of midpoints strictly below y (ties go down); a NaN gives 0
+DWM_DEVINL uint32_t q8_encode(const float* tab, float y) {
+    const float* mid = tab + 256;
+    uint32_t c = 0;
+#pragma unroll
+    for (uint32_t s = 128; s > 0; s >>= 1) c += mid[c + s - 1] < y ? s : 0u;
+    return c;
+}
+
+DWM_DEVINL float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// The four values of a lane -> four codes in one word.  y = x / absmax is a true division; a block of zeros gets the code of 0.
+// floor_positive (the second moment): a strictly positive value never receives the zero code but the smallest positive entry.
+// Without it an element whose gradient is tiny next to the largest of its block would lose v while keeping m, and take a step
+// of lr * m / eps the next time its gradient is exactly zero.
+DWM_DEVINL uint32_t q8_encode4(const float* tab, const float* x, float absmax, uint32_t zero_code, bool floor_positive) {
+    uint32_t w = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        uint32_t c = q8_encode(tab, absmax > 0.f ? x[j] / absmax : 0.f);
+        if (floor_positive && x[j] > 0.f && c == zero_code) c = zero_code + 1;
+        w |= c << (8 * j);
+    }
+    return w;
+}
+
+// elements e .. e + 3 of an n-element tensor: `full` (the whole block inside the tensor, pointers aligned) = one vector access,
+// otherwise element by element with the tail masked (loads give `fill`)
+DWM_DEVINL void q8_load4f(const float* __restrict__ src, int64_t e, int64_t n, bool full, float* f) {
+    if (full) {
+        const float4 a = *(const float4*)(src + e);
+        f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) f[j] = e + j < n ? src[e + j] : 0.f;
+    }
+}
+DWM_DEVINL void q8_store4f(float* __restrict__ dst, int64_t e, int64_t n, bool full, const float* f) {
+    if (full) {
+        *(float4*)(dst + e) = make_float4(f[0], f[1], f[2], f[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) if (e + j < n) dst[e + j] = f[j];
+    }
+}
+DWM_DEVINL uint32_t q8_load4c(const uint8_t* __restrict__ q, int64_t e, int64_t n, bool full, uint32_t fill) {
+    if (full) return *(const uint32_t*)(q + e);
+    uint32_t w = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) w |= (e + j < n ? (uint32_t)q[e + j] : fill) << (8 * j);
+    return w;
+}
+DWM_DEVINL void q8_store4c(uint8_t* __restrict__ q, int64_t e, int64_t n, bool full, uint32_t w) {
+    if (full) {
+        *(uint32_t*)(q + e) = w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) if (e + j < n) q[e + j] = (uint8_t)(w >> (8 * j));
+    }
+}
+DWM_DEVINL bool q8_aligned(const void* p, uintptr_t bytes) { return (((uintptr_t)p) & (bytes - 1)) == 0; }
+
+__global__ void __launch_bounds__(256)
+quantize_blockwise8_kernel(const float* __restrict__ x, int64_t n, const float* __restrict__ code, int floor_positive,
+                           uint8_t* __restrict__ q, float* __restrict__ absmax) {
+    __shared__ float tab[512];
+    q8_stage_table(code, tab);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t zc = q8_encode(tab, 0.f);
+    const bool vec = q8_aligned(x, 16) && q8_aligned(q, 4);
+    const int64_t nblk = (n + Q8_BLOCK - 1) / Q8_BLOCK;
+    for (int64_t blk = (int64_t)blockIdx.x * 4 + wave; blk < nblk; blk += (int64_t)gridDim.x * 4) {
+        const int64_t b0 = blk * Q8_BLOCK, e = b0 + lane * 4;
+        const bool full = vec && b0 + Q8_BLOCK <= n;
+        float f[4];
+        q8_load4f(x, e, n, full, f);
+        const float am = wave_max(fmaxf(fmaxf(fabsf(f[0]), fabsf(f[1])), fmaxf(fabsf(f[2]), fabsf(f[3]))));
+        q8_store4c(q, e, n, full, q8_encode4(tab, f, am, zc, floor_positive != 0));
+        if (lane == 0) absmax[blk] = am;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+dequantize_blockwise8_kernel(const uint8_t* __restrict__ q, const float* __restrict__ absmax, int64_t n,
+                             const float* __restrict__ code, float* __restrict__ x) {
+    __shared__ float tab[256];
+    tab[threadIdx.x] = code[threadIdx.x];
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool vec = q8_aligned(x, 16) && q8_aligned(q, 4);
+    const int64_t nblk = (n + Q8_BLOCK - 1) / Q8_BLOCK;
+    for (int64_t blk = (int64_t)blockIdx.x * 4 + wave; blk < nblk; blk += (int64_t)gridDim.x * 4) {
+        const int64_t b0 = blk * Q8_BLOCK, e = b0 + lane * 4;
+        const bool full = vec && b0 + Q8_BLOCK <= n;
+        const uint32_t w = q8_load4c(q, e, n, full, 0u);
+        const float s = absmax[blk];
+        float f[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) f[j] = tab[(w >> (8 * j)) & 255u] * s;
+        q8_store4f(x, e, n, full, f);
+    }
+}
+
+// adamw_multi_kernel with both moments in the 8-bit format: decode, the same update, re-encode, in one pass (18 bytes per
+// parameter instead of 30).  The parameter update uses the fresh fp32 moments; quantisation only affects what the next step
+// starts from.  Wave w of a workgroup takes blocks w, w + 4, ... of the workgroup's chunk (a multiple of 256 elements).
+__global__ void __launch_bounds__(256)
+adamw8_multi_kernel(const dwm_adamw8_item* __restrict__ items, const int32_t* __restrict__ block_item,
+                    const int64_t* __restrict__ block_start, int64_t chunk, const float* __restrict__ code_m,
+                    const float* __restrict__ code_v, float lr, float b1, float b2, float eps, float wd,
+                    float bc1, float bc2, float gscale) {
+    __shared__ float tab_m[512], tab_v[512];
+    q8_stage_table(code_m, tab_m);
+    q8_stage_table(code_v, tab_v);
+    __syncthreads();
+    const dwm_adamw8_item it = items[block_item[blockIdx.x]];
+    const int64_t i0 = block_start[blockIdx.x];
+    const int64_t i1 = i0 + chunk < it.n ? i0 + chunk : it.n;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float* __restrict__ p = it.p;
+    const float* __restrict__ g = it.g;
+    uint8_t* __restrict__ mq = it.m_q;
+    uint8_t* __restrict__ vq = it.v_q;
+    bf16_t* __restrict__ pb = (bf16_t*)it.p_bf16;
+    const uint32_t zm = q8_encode(tab_m, 0.f), zv = q8_encode(tab_v, 0.f);
+    const bool vec = q8_aligned(p, 16) && q8_aligned(g, 16) && q8_aligned(mq, 4) && q8_aligned(vq, 4) && q8_aligned(pb, 8);
+    for (int64_t b0 = i0 + wave * Q8_BLOCK; b0 < i1; b0 += 4 * Q8_BLOCK) {
+        const int64_t e = b0 + lane * 4, blk = b0 / Q8_BLOCK;
+        const bool full = vec && b0 + Q8_BLOCK <= it.n;
+        float pi[4], gi[4], mi[4], vi[4];
+        q8_load4f(p, e, it.n, full, pi);
+        q8_load4f(g, e, it.n, full, gi);
+        const uint32_t wm = q8_load4c(mq, e, it.n, full, zm), wv = q8_load4c(vq, e, it.n, full, zv);
+        const float sm = it.m_absmax[blk], sv = it.v_absmax[blk];
+        float am = 0.f, av = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float gj = gi[j] * gscale;
+            float pj = pi[j] * (1.f - lr * wd);
+            mi[j] = b1 * (tab_m[(wm >> (8 * j)) & 255u] * sm) + (1.f - b1) * gj;
+            vi[j] = b2 * (tab_v[(wv >> (8 * j)) & 255u] * sv) + (1.f - b2) * gj * gj;
+            pj -= lr * (mi[j] / bc1) / (sqrtf(vi[j] / bc2) + eps);
+            pi[j] = pj;
+            am = fmaxf(am, fabsf(mi[j]));
+            av = fmaxf(av, vi[j]);
+        }
+        am = wave_max(am);
+        av = wave_max(av);
+        q8_store4f(p, e, it.n, full, pi);
+        if (pb) {
+            if (full) {
+                *(uint2*)(pb + e) = pack4(pi);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) if (e + j < it.n) pb[e + j] = f32_to_bf16(pi[j]);
+            }
+        }
+        q8_store4c(mq, e, it.n, full, q8_encode4(tab_m, mi, am, zm, false));
+        q8_store4c(vq, e, it.n, full, q8_encode4(tab_v, vi, av, zv, true));
+        if (lane == 0) { it.m_absmax[blk] = am; it.v_absmax[blk] = av; }
+    }
+}
+
 __global__ void __launch_bounds__(256)
 cast_bf16_to_f32_kernel(const bf16_t* __restrict__ x, int64_t ldx, float* __restrict__ y, int64_t ldy,
                         int64_t rows, int64_t cols, int accumulate) {
@@ -670,6 +853,33 @@ extern "C" int dwm_adamw_multi(const dwm_adamw_item* items, const int32_t* block
         bias_corr2 <= 0.f) return DWM_EINVAL;
     hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, items, block_item, block_start,
                        chunk, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale);
+    return dwm_launch_status();
+}
+
+extern "C" int dwm_quantize_blockwise8(const float* x, int64_t n, const float* code, int32_t floor_positive, uint8_t* q,
+                                       float* absmax, void* stream) {
+    if (!x || !code || !q || !absmax || n <= 0) return DWM_EINVAL;
+    hipLaunchKernelGGL(quantize_blockwise8_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, n, code,
+                       floor_positive, q, absmax);
+    return dwm_launch_status();
+}
+
+extern "C" int dwm_dequantize_blockwise8(const uint8_t* q, const float* absmax, int64_t n, const float* code, float* x,
+                                         void* stream) {
+    if (!q || !absmax || !code || !x || n <= 0) return DWM_EINVAL;
+    hipLaunchKernelGGL(dequantize_blockwise8_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, q, absmax, n,
+                       code, x);
+    return dwm_launch_status();
+}
+
+extern "C" int dwm_adamw8_multi(const dwm_adamw8_item* items, const int32_t* block_item, const int64_t* block_start,
+                                int64_t n_blocks, int64_t chunk, const float* code_m, const float* code_v, float lr, float beta1,
+                                float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2, float grad_scale,
+                                void* stream) {
+    if (!items || !block_item || !block_start || !code_m || !code_v || n_blocks <= 0 || n_blocks >= (1ll << 31) || chunk <= 0 ||
+        chunk % Q8_BLOCK != 0 || bias_corr1 <= 0.f || bias_corr2 <= 0.f) return DWM_EINVAL;
+    hipLaunchKernelGGL(adamw8_multi_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, items, block_item,
+                       block_start, chunk, code_m, code_v, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale);
     return dwm_launch_status();
 }
 

@@ -358,11 +358,14 @@ class CTSDTrainer:
                  max_grad_norm: Optional[float] = None, weighting_scheme: str = "logit_normal", ddp: bool = False,
                  ddp_kwargs: Optional[dict] = None, common_config: Optional[dict] = None, training_config: Optional[dict] = None,
                  reference_latent_count=0, lr_scheduler=None, ddp_comm_dtype: Optional[torch.dtype] = None,
-                 train_scheduler=None):
+                 train_scheduler=None, optimizer_bits: int = 32):
         """common_config["frame_prediction_style"] (None | "diffusion_forcing" | "ctsd") and training_config select the
         training task mix of `make_input_for_prediction`; with "diffusion_forcing" every frame draws its own timestep
-        (ctsd.py:1232-1237)."""
+        (ctsd.py:1232-1237).  optimizer_bits: 32 = train.AdamW (fp32 moments), 8 = train.AdamW8bit (block-wise 8-bit moments: the
+        reference's single-GPU recipe, docs/CtsdPipelineFaqs.md "Single GPU training")."""
         from . import train as _train
+        if optimizer_bits not in (8, 32):
+            raise ValueError(f"optimizer_bits: 8 or 32, got {optimizer_bits!r}")
         self.model = model.train()
         self.wrapper = model
         self.common_config, self.training_config = dict(common_config or {}), dict(training_config or {})
@@ -381,7 +384,8 @@ class CTSDTrainer:
             elif ddp_comm_dtype not in (None, torch.float32):
                 raise ValueError("ddp_comm_dtype: torch.bfloat16, torch.float32 or None")
         # every parameter, frozen ones included, as the reference builds it (ctsd.py:1089-1092): state-dict indices match
-        self.optimizer = _train.AdamW(model.parameters(), lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        opt_cls = _train.AdamW8bit if optimizer_bits == 8 else _train.AdamW
+        self.optimizer = opt_cls(model.parameters(), lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         self.lr_scheduler = lr_scheduler(self.optimizer) if callable(lr_scheduler) else lr_scheduler
         self.global_step = 0
         self.sigmas = flow_match_train_sigmas(num_train_timesteps, shift)

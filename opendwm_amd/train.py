@@ -19,7 +19,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-from . import ops
+from . import ops, quant8
 from . import train_ops as T
 from .blocks import (STORE, AlphaBlender, JointTransformerBlock, TimestepEmbedding, VTSelfAttentionBlock, _bf)
 from .ops import ACT_GELU_TANH, ACT_SILU
@@ -890,3 +890,117 @@ class AdamW(torch.optim.Optimizer):
                                weight_decay=group["weight_decay"], step=step, grad_scale=grad_scale)
         STORE.bump(keep_shadows=True)
         return loss
+
+
+class AdamW8bit(AdamW):
+    """`AdamW` with both moments kept in the block-wise 8-bit format of opendwm_amd.quant8 (one byte per element and moment plus
+    one fp32 scale per 256 elements: 2.03 bytes of state per parameter instead of 8), updated by `dwm_adamw8_multi`.  It fills the
+    slot the reference's docs/CtsdPipelineFaqs.md ("Single GPU training", step 2) gives to `bitsandbytes.optim.Adam8bit`.
+
+    State per quantised parameter: `step`, `exp_avg` (uint8, the parameter's shape), `exp_avg_absmax` (fp32 [ceil(n / 256)]),
+    `exp_avg_sq`, `exp_avg_sq_absmax`.  Parameters of fewer than `min_8bit_size` elements and non-contiguous ones keep fp32
+    moments and take `AdamW`'s path unchanged.  The parameter update is computed from the fresh fp32 moments; quantisation only
+    affects what the next step starts from.
+
+    `load_state_dict` takes its own files and fp32-moment files (torch.optim.AdamW's, the reference's, `AdamW`'s: quantised on
+    load); `state_dict_fp32()` hands the state back in torch.optim.AdamW's layout."""
+
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, min_8bit_size=4096):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self.min_8bit_size = int(min_8bit_size)
+
+    def _wants_8bit(self, p) -> bool:
+        return p.numel() >= self.min_8bit_size and p.is_contiguous()
+
+    def _init_state(self, p) -> dict:
+        """fresh state of p: zero moments (8-bit: the code of 0.0 everywhere, scales 0)"""
+        st = self.state[p]
+        st["step"] = torch.tensor(0.0)
+        if self._wants_8bit(p):
+            nb = quant8.n_blocks(p.numel())
+            for key, signed in (("exp_avg", True), ("exp_avg_sq", False)):
+                st[key] = torch.full(p.shape, quant8.zero_code(signed), dtype=torch.uint8, device=p.device)
+                st[key + "_absmax"] = torch.zeros(nb, dtype=torch.float32, device=p.device)
+        else:
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        return st
+
+    @torch.no_grad()
+    def step(self, closure=None, grad_scale: float = 1.0):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            if group.get("amsgrad") or group.get("maximize"):
+                raise NotImplementedError("AdamW8bit: amsgrad / maximize")
+            b1, b2 = group["betas"]
+            hyper = dict(lr=float(group["lr"]), beta1=b1, beta2=b2, eps=group["eps"], weight_decay=group["weight_decay"],
+                         grad_scale=grad_scale)
+            batches8: dict = {}                 # step count -> lists for ONE dwm_adamw8_multi launch (normally a single batch)
+            batches32: dict = {}                # the same for the fp32-moment tensors (dwm_adamw_multi)
+            for p in group["params"]:
+                if p.grad is None:              # frozen, or unused in this step: no state, no step (as torch)
+                    continue
+                if p.dtype != torch.float32:
+                    raise RuntimeError("AdamW8bit: fp32 master parameters expected")
+                st = self.state[p]
+                if len(st) == 0:
+                    st = self._init_state(p)
+                st["step"] += 1
+                g = p.grad if p.grad.dtype == torch.float32 else p.grad.float()
+                shadow = STORE.bf(p) if (p.is_cuda and p.numel() % 4 == 0 and p.is_contiguous()) else None
+                if shadow is None:
+                    STORE._shadow.pop(id(p), None)      # re-cast on next use
+                step = int(st["step"].item())
+                if st["exp_avg"].dtype == torch.uint8:
+                    b = batches8.setdefault(step, ([], [], [], [], [], [], []))
+                    for lst, t in zip(b, (p.data, g.contiguous(), st["exp_avg"], st["exp_avg_absmax"], st["exp_avg_sq"],
+                                          st["exp_avg_sq_absmax"], shadow)):
+                        lst.append(t)
+                elif p.is_contiguous() and st["exp_avg"].is_contiguous() and st["exp_avg_sq"].is_contiguous():
+                    b = batches32.setdefault(step, ([], [], [], [], []))
+                    for lst, t in zip(b, (p.data, g.contiguous(), st["exp_avg"], st["exp_avg_sq"], shadow)):
+                        lst.append(t)
+                else:
+                    T.adamw_(p.data, g.contiguous(), st["exp_avg"], st["exp_avg_sq"], shadow, step=step, **hyper)
+            for step, lists in batches8.items():
+                T.adamw8_multi_(*lists, step=step, **hyper)
+            for step, lists in batches32.items():
+                T.adamw_multi_(*lists, step=step, **hyper)
+        STORE.bump(keep_shadows=True)
+        return loss
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict) -> None:
+        """own files (8-bit state) and fp32-moment files; the latter are quantised here for every tensor that wants 8 bits"""
+        super().load_state_dict(state_dict)
+        for p, st in self.state.items():
+            if "exp_avg_absmax" in st:          # torch casts every state tensor to the parameter's dtype: codes back to bytes (exact)
+                for key in ("exp_avg", "exp_avg_sq"):
+                    st[key] = st[key].to(torch.uint8)
+                    st[key + "_absmax"] = st[key + "_absmax"].to(torch.float32)
+            elif "exp_avg" in st and self._wants_8bit(p):
+                code_m, code_v = quant8.device_codes(p.device)
+                for key, code, floor in (("exp_avg", code_m, False), ("exp_avg_sq", code_v, True)):
+                    st[key], st[key + "_absmax"] = T.quantize_blockwise8(st[key].float().contiguous(), code, floor_positive=floor)
+
+    @torch.no_grad()
+    def state_dict_fp32(self) -> dict:
+        """the state dict with every moment dequantised, in torch.optim.AdamW's layout: what torch.optim.AdamW, the reference's
+        resume path and `AdamW` load"""
+        sd = self.state_dict()
+        params = [p for group in self.param_groups for p in group["params"]]
+        ids = [i for group in sd["param_groups"] for i in group["params"]]
+        state = {}
+        for i, p in zip(ids, params):
+            if i not in sd["state"]:
+                continue
+            st = dict(sd["state"][i])
+            if "exp_avg_absmax" in st:
+                code_m, code_v = quant8.device_codes(p.device)
+                for key, code in (("exp_avg", code_m), ("exp_avg_sq", code_v)):
+                    st[key] = T.dequantize_blockwise8(st[key], st.pop(key + "_absmax"), code)
+            state[i] = st
+        return {"state": state, "param_groups": sd["param_groups"]}

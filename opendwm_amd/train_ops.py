@@ -9,7 +9,7 @@ from typing import Optional, Sequence, Tuple
 
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, quant8
 from .ops import _call, _chk2d, _p, cast_f32, ACT_GELU_TANH, ACT_SILU  # noqa: F401  (cast_f32: fp32 (+)= bf16, used as train_ops.cast_f32)
 
 bf16 = torch.bfloat16
@@ -172,8 +172,24 @@ def adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, p
           1.0 - beta1 ** step, 1.0 - beta2 ** step, grad_scale)
 
 
-ADAMW_CHUNK = 1 << 16            # elements per workgroup of the multi-tensor AdamW
+ADAMW_CHUNK = 1 << 16            # elements per workgroup of the multi-tensor AdamW (a multiple of the 8-bit block of 256)
 _ADAMW_BLOCKS: dict = {}         # (device, tuple of numels) -> (block_item, block_start) on the device: static per parameter list
+
+
+def _adamw_blocks(dev: torch.device, numels: tuple):
+    """the cached (block_item, block_start) tables of a parameter list: ceil(n / ADAMW_CHUNK) workgroups per tensor"""
+    key = (dev.index, numels)
+    tab = _ADAMW_BLOCKS.get(key)
+    if tab is None:
+        bi, bs = [], []
+        for i, n in enumerate(numels):
+            nb = (n + ADAMW_CHUNK - 1) // ADAMW_CHUNK
+            bi.append(torch.full((nb,), i, dtype=torch.int32))
+            bs.append(torch.arange(nb, dtype=torch.int64) * ADAMW_CHUNK)
+        while len(_ADAMW_BLOCKS) >= 2:                    # an optimizer has at most two lists (fp32 and 8-bit moments)
+            _ADAMW_BLOCKS.pop(next(iter(_ADAMW_BLOCKS)))
+        tab = _ADAMW_BLOCKS[key] = (torch.cat(bi).to(dev), torch.cat(bs).to(dev))
+    return tab
 
 
 def adamw_multi_(ps, gs, ms, vs, shadows, *, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, step: int,
@@ -190,18 +206,67 @@ def adamw_multi_(ps, gs, ms, vs, shadows, *, lr: float, beta1: float, beta2: flo
                 raise RuntimeError("adamw_multi_: fp32 contiguous tensors of one shape on one device expected")
         rows.append((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), 0 if sh is None else sh.data_ptr(), p.numel()))
     items = torch.tensor(rows, dtype=torch.int64).to(dev, non_blocking=True)          # [n, 6] = dwm_adamw_item[n]
-    key = (dev.index, tuple(r[5] for r in rows))
-    tab = _ADAMW_BLOCKS.get(key)
-    if tab is None:
-        bi, bs = [], []
-        for i, r in enumerate(rows):
-            nb = (r[5] + ADAMW_CHUNK - 1) // ADAMW_CHUNK
-            bi.append(torch.full((nb,), i, dtype=torch.int32))
-            bs.append(torch.arange(nb, dtype=torch.int64) * ADAMW_CHUNK)
-        _ADAMW_BLOCKS.clear()                                                           # one parameter list at a time
-        tab = _ADAMW_BLOCKS[key] = (torch.cat(bi).to(dev), torch.cat(bs).to(dev))
+    tab = _adamw_blocks(dev, tuple(r[5] for r in rows))
     _call("dwm_adamw_multi", _p(items), _p(tab[0]), _p(tab[1]), tab[0].numel(), ADAMW_CHUNK, lr, beta1, beta2, eps,
           weight_decay, 1.0 - beta1 ** step, 1.0 - beta2 ** step, grad_scale)
+
+
+# ---- block-wise 8-bit optimizer state (opendwm_amd.quant8: value = code[q] * absmax[block of 256])
+def _chk_q8(q: torch.Tensor, absmax: torch.Tensor, n: int, dev, what: str) -> None:
+    if (q.dtype != torch.uint8 or not q.is_contiguous() or q.numel() != n or q.device != dev or absmax.dtype != torch.float32
+            or not absmax.is_contiguous() or absmax.numel() != quant8.n_blocks(n) or absmax.device != dev):
+        raise RuntimeError(f"{what}: contiguous uint8 codes [n] and fp32 scales [ceil(n / 256)] on the tensor's device expected")
+
+
+def _chk_code(code: torch.Tensor, dev, what: str) -> None:
+    if code.dtype != torch.float32 or not code.is_contiguous() or code.numel() != 256 or code.device != dev:
+        raise RuntimeError(f"{what}: the code table must be 256 contiguous fp32 values on the tensor's device")
+
+
+def quantize_blockwise8(x: torch.Tensor, code: torch.Tensor, floor_positive: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """x (fp32, contiguous) -> (codes uint8 of x's shape, absmax fp32 [ceil(n / 256)]); floor_positive: a strictly positive value
+    never gets the zero code (see dwm_quantize_blockwise8)"""
+    if x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda or x.numel() == 0:
+        raise RuntimeError("quantize_blockwise8: a non-empty fp32 contiguous device tensor expected")
+    _chk_code(code, x.device, "quantize_blockwise8")
+    q = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    absmax = torch.empty(quant8.n_blocks(x.numel()), dtype=torch.float32, device=x.device)
+    _call("dwm_quantize_blockwise8", _p(x), x.numel(), _p(code), int(floor_positive), _p(q), _p(absmax))
+    return q, absmax
+
+
+def dequantize_blockwise8(q: torch.Tensor, absmax: torch.Tensor, code: torch.Tensor) -> torch.Tensor:
+    """fp32 tensor of q's shape: code[q] * absmax[block]"""
+    if not q.is_cuda or q.numel() == 0:
+        raise RuntimeError("dequantize_blockwise8: a non-empty device tensor expected")
+    _chk_q8(q, absmax, q.numel(), q.device, "dequantize_blockwise8")
+    _chk_code(code, q.device, "dequantize_blockwise8")
+    x = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+    _call("dwm_dequantize_blockwise8", _p(q), _p(absmax), q.numel(), _p(code), _p(x))
+    return x
+
+
+def adamw8_multi_(ps, gs, mqs, mas, vqs, vas, shadows, *, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
+                  step: int, grad_scale: float = 1.0) -> None:
+    """dwm_adamw8_multi: adamw_multi_ with the moments of every entry in the 8-bit format (mq / vq: uint8 codes, ma / va: fp32
+    block scales); the signed table encodes m, the unsigned one v."""
+    if not ps:
+        return
+    dev = ps[0].device
+    rows = []
+    for p, g, mq, ma, vq, va, sh in zip(ps, gs, mqs, mas, vqs, vas, shadows):
+        for t in (p, g):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel() or t.device != dev:
+                raise RuntimeError("adamw8_multi_: fp32 contiguous tensors of one shape on one device expected")
+        _chk_q8(mq, ma, p.numel(), dev, "adamw8_multi_")
+        _chk_q8(vq, va, p.numel(), dev, "adamw8_multi_")
+        rows.append((p.data_ptr(), g.data_ptr(), mq.data_ptr(), ma.data_ptr(), vq.data_ptr(), va.data_ptr(),
+                     0 if sh is None else sh.data_ptr(), p.numel()))
+    items = torch.tensor(rows, dtype=torch.int64).to(dev, non_blocking=True)          # [n, 8] = dwm_adamw8_item[n]
+    tab = _adamw_blocks(dev, tuple(r[7] for r in rows))
+    code_m, code_v = quant8.device_codes(dev)
+    _call("dwm_adamw8_multi", _p(items), _p(tab[0]), _p(tab[1]), tab[0].numel(), ADAMW_CHUNK, _p(code_m), _p(code_v), lr, beta1,
+          beta2, eps, weight_decay, 1.0 - beta1 ** step, 1.0 - beta2 ** step, grad_scale)
 
 
 # ------------------------------------------------------------------------------------------ composites
