@@ -38,7 +38,8 @@ extern "C" {
 #define DWM_EALIGN (-2)     /* pointer or leading dimension not 16-byte aligned */
 #define DWM_EUNSUPPORTED (-3)
 
-/* ABI version; bump on any struct change. */
+/* ABI version; bump on any struct change.  Pure additions (a new struct with new entry points, such as dwm_vae_attn_args /
+ * dwm_vae_attention*) leave it alone: no existing caller sees a difference, and dwm_source_hash() already tells builds apart. */
 #define DWM_ABI_VERSION 18
 int dwm_abi_version(void);
 /* SHA-256 (hex) of the sources this library was built from (csrc .hip and .h files + this header, in sorted order), as
@@ -411,6 +412,24 @@ int dwm_pad_tokens(const void* x, void* y, int64_t rows, int32_t C, const dwm_ro
 
 /* y[r, :L] = softmax(scale * x[r, :L]) (fp32 math, bf16 storage; single-head mid-block attention). */
 int dwm_softmax_rows(const void* x, void* y, int64_t rows, int32_t L, int64_t ld, float scale, void* stream);
+
+/* Single-head attention of the VAE mid block.  I images of P pixels, head dimension C:
+ *   out[i*P + r, :] = sum_j softmax_j(scale * <q[i*P + r, :], k[i*P + j, :]>) * v[i*P + j, :],   j in [0, P)
+ * q, k, v, out: rows of C elements with row strides ldq / ldk / ldv / ldo (in elements; q, k, v may be column blocks of one
+ * [I*P, 3C] matrix).  Any P >= 1: no P x P matrix is materialised, keys past P are masked by selection (never by a product).
+ * One launch for all images (grid I x ceil(P / query tile)), online softmax in the exp2 domain, a query's keys reduced in a
+ * fixed order (deterministic, no atomics); nothing is read outside rows [0, I*P) of q / k / v, nothing written outside those
+ * rows of out.  C in {128, 256, 512}, else DWM_EUNSUPPORTED; null pointers / sizes <= 0: DWM_EINVAL; a pointer off 16 bytes or
+ * a stride that is not a multiple of 8 (bf16) / 4 (fp32) elements: DWM_EALIGN.  Replaces the one-head diffusers Attention of
+ * UNetMidBlock2D in AutoencoderKL's encoder and decoder at the sizes dwm_softmax_rows does not take. */
+typedef struct dwm_vae_attn_args {
+    const void* q; const void* k; const void* v; void* out;
+    int64_t ldq, ldk, ldv, ldo;
+    int64_t I, P;
+    int32_t C; float scale;
+} dwm_vae_attn_args;
+int dwm_vae_attention(const dwm_vae_attn_args* args, void* stream);       /* bf16 in / out, fp32 softmax and accumulation */
+int dwm_vae_attention_f32(const dwm_vae_attn_args* args, void* stream);   /* fp32 in / out: the accuracy path */
 
 /* Explicit perspective modelling (RayEncoder / get_rays, src/dwm/models/crossview_temporal_dit.py:11-102): the 72 inputs of
  * RayEncoder.proj for every latent token of I images of h x w tokens.  cam fp32 [I, 21] = { inverse of the token-resolution

@@ -116,6 +116,11 @@ class AdamW8Item(C.Structure):          # one row of the device array train_ops.
     _fields_ = [("p", _vp), ("g", _vp), ("m_q", _vp), ("m_absmax", _vp), ("v_q", _vp), ("v_absmax", _vp), ("p_bf16", _vp), ("n", _i64)]
 
 
+class VaeAttnArgs(C.Structure):
+    _fields_ = [("q", _vp), ("k", _vp), ("v", _vp), ("out", _vp), ("ldq", _i64), ("ldk", _i64), ("ldv", _i64), ("ldo", _i64),
+                ("I", _i64), ("P", _i64), ("C", _i32), ("scale", _f32)]
+
+
 # name -> (restype, argtypes); every symbol include/dwm_hip.h declares
 SIGNATURES = {
     "dwm_abi_version": (_i32, []),
@@ -175,6 +180,8 @@ SIGNATURES = {
     "dwm_groupnorm_spatial_f32": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _f32, _vp, _vp, _i32, _vp, C.POINTER(RowMap2D),
                                          C.POINTER(GnImgMap), C.POINTER(GnZMap), _vp]),
     "dwm_softmax_rows": (_i32, [_vp, _vp, _i64, _i32, _i64, _f32, _vp]),
+    "dwm_vae_attention": (_i32, [C.POINTER(VaeAttnArgs), _vp]),
+    "dwm_vae_attention_f32": (_i32, [C.POINTER(VaeAttnArgs), _vp]),
     # training
     "dwm_transpose_bf16": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp]),
     "dwm_segsum": (_i32, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),

@@ -1069,6 +1069,36 @@ def softmax_rows(x: torch.Tensor, scale: float, out: Optional[torch.Tensor] = No
     return out
 
 
+VAE_ATTENTION_CHANNELS = (128, 256, 512)       # head dimensions dwm_vae_attention is instantiated for
+
+
+def vae_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, I: int, P: int, scale: float) -> torch.Tensor:
+    """Single-head attention over I images of P pixels (the VAE mid block): out[i] = softmax(scale * q[i] k[i]^T) v[i], one launch,
+    no P x P matrix in memory, any P >= 1.  q, k, v, out: 2-D [I*P, C] with contiguous rows, all bf16 or all fp32 (the accuracy
+    path); q, k, v may be column blocks of one [I*P, 3C] buffer.  C in VAE_ATTENTION_CHANNELS."""
+    dt = _dt(q)
+    if any(t.dtype != dt for t in (q, k, v, out)):
+        raise RuntimeError(f"vae_attention: q, k, v, out must all be bf16 or all fp32, got {[str(t.dtype) for t in (q, k, v, out)]}")
+    if I <= 0 or P <= 0:
+        raise RuntimeError(f"vae_attention: I and P must be positive, got I={I} P={P}")
+    Cc = q.shape[-1]
+    for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        if tuple(t.shape) != (I * P, Cc):
+            raise RuntimeError(f"vae_attention: {name} must be [I*P, C] = [{I * P}, {Cc}], got {tuple(t.shape)}")
+    for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        _chk2d(t, name, dt)
+    if Cc not in VAE_ATTENTION_CHANNELS:
+        raise RuntimeError(f"vae_attention: head dimension {Cc} is not one of {VAE_ATTENTION_CHANNELS}")
+    if any(_overlaps(out, t) for t in (q, k, v)):
+        raise RuntimeError("vae_attention: out must not overlap q, k or v")
+    a = _lib.VaeAttnArgs()
+    a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
+    a.ldq, a.ldk, a.ldv, a.ldo = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
+    a.I, a.P, a.C, a.scale = I, P, Cc, float(scale)
+    _call("dwm_vae_attention_f32" if dt == f32 else "dwm_vae_attention", C.byref(a))
+    return out
+
+
 def cast_bf16(x: torch.Tensor) -> torch.Tensor:
     if x.dtype == bf16:
         return x

@@ -7,7 +7,8 @@ decoder.mid_block.attentions.0.{group_norm,to_q,to_k,to_v,to_out.0}, decoder.up_
 decoder.up_blocks.N.upsamplers.0.conv, decoder.conv_norm_out, decoder.conv_out) so a released
 `vae/diffusion_pytorch_model.safetensors` loads with strict=True.  Activations are token-major [I*H*W, C] bf16; every 3x3 convolution is an
 implicit GEMM of dwm_gemm_bf16 over a zero-padded token grid; GroupNorm+SiLU, the nearest
-upsample and the mid-block softmax are HIP kernels (csrc/vae.hip)."""
+upsample and the mid-block softmax are HIP kernels (csrc/vae.hip); at image sizes the softmax route does not take, the mid-block
+attention is one fused kernel (csrc/vae_attention.hip), so any size encodes and decodes."""
 from __future__ import annotations
 
 import types
@@ -66,6 +67,40 @@ class ResnetBlock2D(nn.Module):
         return ops.gemm(p2, pk["w2"], _bf(self.conv2.bias), epilogue=EPI_RESID, res=sc, a_grid=grid, conv3x3=True, out=h1)
 
 
+MID_ATTENTION_MODES = ("auto", "fused", "gemm")
+GEMM_ROUTE_MAX_PIXELS = 4096          # dwm_softmax_rows holds a row of at most 4096 scores
+
+
+def mid_attention_route(P: int, C: int, dtype: torch.dtype = bf16, mode: str = "auto") -> str:
+    """Which route the mid-block attention takes for P pixels per image and C channels: "gemm" (per-image score GEMM, softmax_rows,
+    P.V GEMM: needs P % 64 == 0 and P <= 4096) or "fused" (ops.vae_attention: any P, C in ops.VAE_ATTENTION_CHANNELS).  A pure
+    function of its arguments, the same for both compute dtypes.  "auto" keeps the GEMM route wherever it applies, so whatever ran
+    before the fused kernel existed runs the same code; "fused" / "gemm" force a route ("fused" with a C the kernel does not
+    cover falls back to the GEMM route where that applies)."""
+    if mode not in MID_ATTENTION_MODES:
+        raise ValueError(f"mid_attention must be one of {MID_ATTENTION_MODES}, got {mode!r}")
+    if dtype not in (bf16, torch.float32):
+        raise ValueError(f"mid attention computes in bf16 or fp32, got {dtype}")
+    gemm_ok = P % 64 == 0 and P <= GEMM_ROUTE_MAX_PIXELS
+    fused_ok = C in ops.VAE_ATTENTION_CHANNELS
+    if mode == "gemm":
+        if not gemm_ok:
+            raise NotImplementedError(f"VAE mid attention, mid_attention='gemm': needs pixels-per-image % 64 == 0 (GEMM K granularity) "
+                                      f"and <= {GEMM_ROUTE_MAX_PIXELS} (softmax row), got {P}; mid_attention='auto' or 'fused' takes any size")
+        return "gemm"
+    if mode == "fused":
+        if fused_ok:
+            return "fused"
+    elif gemm_ok:
+        return "gemm"
+    elif fused_ok:
+        return "fused"
+    if gemm_ok:                           # mode == "fused" and a C the kernel is not instantiated for
+        return "gemm"
+    raise NotImplementedError(f"VAE mid attention (mid_attention={mode!r}): the fused kernel covers channels in {ops.VAE_ATTENTION_CHANNELS} "
+                              f"(got {C}) and the GEMM route pixels-per-image % 64 == 0 and <= {GEMM_ROUTE_MAX_PIXELS} (got {P})")
+
+
 class _VaeAttention(nn.Module):
     """diffusers Attention as the VAE mid block builds it: one head of dim C, GroupNorm(32) first,
     biased q/k/v/out projections, residual connection."""
@@ -78,11 +113,29 @@ class _VaeAttention(nn.Module):
         self.to_k = nn.Linear(channels, channels)
         self.to_v = nn.Linear(channels, channels)
         self.to_out = nn.ModuleList([nn.Linear(channels, channels), nn.Identity()])
+        self._pk = {}
 
-    def run(self, x: torch.Tensor, I: int, P: int) -> torch.Tensor:
+    def packed(self):
+        """q | k | v weights [3C, C] and biases [3C] of the fused route, one set per compute precision"""
+        pk = self._pk.get(STORE.precision)
+        if pk is None:
+            qkv = (self.to_q, self.to_k, self.to_v)
+            pk = self._pk[STORE.precision] = {"w": torch.cat([_bf(m.weight) for m in qkv], 0).contiguous(),
+                                              "b": torch.cat([_bf(m.bias) for m in qkv], 0).contiguous()}
+        return pk
+
+    def run(self, x: torch.Tensor, I: int, P: int, mode: str = "auto") -> torch.Tensor:
         Cc = self.channels
-        if P % 64 != 0:
-            raise NotImplementedError("VAE mid attention needs pixels-per-image % 64 == 0 (GEMM K granularity)")
+        to = self.to_out[0]
+        if mid_attention_route(P, Cc, STORE.precision, mode) == "fused":
+            # four launches whatever I is: GroupNorm, one q|k|v GEMM (the v bias with it), the attention kernel, the out projection
+            xn = ops.groupnorm_silu(x, I, P, _bf(self.group_norm.weight), _bf(self.group_norm.bias), self.groups, self.eps,
+                                    silu=False)
+            pk = self.packed()
+            qkv = ops.gemm(xn, pk["w"], pk["b"])                           # [I*P, 3C]
+            o = torch.empty_like(x)
+            ops.vae_attention(qkv[:, :Cc], qkv[:, Cc:2 * Cc], qkv[:, 2 * Cc:], o, I, P, Cc ** -0.5)
+            return ops.gemm(o, _bf(to.weight), _bf(to.bias), epilogue=EPI_RESID, res=x, out=xn)
         xn = ops.groupnorm_silu(x, I, P, _bf(self.group_norm.weight), _bf(self.group_norm.bias), self.groups, self.eps,
                                 silu=False)
         q = ops.gemm(xn, _bf(self.to_q.weight), _bf(self.to_q.bias))
@@ -96,7 +149,6 @@ class _VaeAttention(nn.Module):
             vt = ops.gemm(wv, xn[sl], w_is_activation=True)              # V^T without bias: [C, P]
             # rows of softmax sum to 1, so P @ (V + 1 b^T) = P @ V + b^T: the v bias is the column bias here
             ops.gemm(s, vt, _bf(self.to_v.bias), out=o[sl], w_is_activation=True)
-        to = self.to_out[0]
         return ops.gemm(o, _bf(to.weight), _bf(to.bias), epilogue=EPI_RESID, res=x, out=xn)      # (never into the A operand)
 
 
@@ -214,6 +266,8 @@ class AutoencoderKL(nn.Module):
         # BASELINE.json configs[0], decodes in fp32: ctsd.py:1189-1193, 1634-1640): fp32 activations and weights, convolutions
         # by dwm_gemm_f32, fp32 GroupNorm / softmax kernels
         self.compute_dtype = bf16
+        # route of the mid-block attention of encoder and decoder, read at every encode / decode: see mid_attention_route
+        self.mid_attention = "auto"
 
     @property
     def dtype(self):
@@ -293,7 +347,7 @@ class AutoencoderKL(nn.Module):
                 grid = PaddedGrid(I, grid.h // 2, grid.w // 2)
         h = e.mid_block.resnets[0].run(h, grid, scratch)
         for attn in e.mid_block.attentions:
-            h = attn.run(h, I, grid.h * grid.w)
+            h = attn.run(h, I, grid.h * grid.w, self.mid_attention)
         h = e.mid_block.resnets[1].run(h, grid, scratch)
         hp = ops.groupnorm_silu(h, I, grid.h * grid.w, _bf(e.conv_norm_out.weight), _bf(e.conv_norm_out.bias), e.groups,
                                 e.eps, out=scratch(grid, h.shape[1]), out_grid=grid)
@@ -348,7 +402,7 @@ class AutoencoderKL(nn.Module):
         x = ops.gemm(zp, _conv3_w(d.conv_in, tok.shape[1]), _bf(d.conv_in.bias), a_grid=grid, conv3x3=True)
         x = d.mid_block.resnets[0].run(x, grid, scratch)
         for attn in d.mid_block.attentions:
-            x = attn.run(x, I, h * w)
+            x = attn.run(x, I, h * w, self.mid_attention)
         x = d.mid_block.resnets[1].run(x, grid, scratch)
         for ub in d.up_blocks:
             for res in ub.resnets:
