@@ -586,6 +586,25 @@ int dwm_adamw8_multi(const dwm_adamw8_item* items, const int32_t* block_item, co
                      int64_t chunk, const float* code_m, const float* code_v, float lr, float beta1, float beta2, float eps,
                      float weight_decay, float bias_corr1, float bias_corr2, float grad_scale, void* stream);
 
+/* Gradient norm, clip coefficient and non-finite check of a LIST of fp32 gradients in one read (the work of
+ * torch.amp.GradScaler.unscale_ + torch.nn.utils.clip_grad_norm_ + the found-inf check of GradScaler.step, ctsd.py:1401-1432).
+ * items / block_item / block_start are DEVICE arrays with the meaning they have for dwm_adamw_multi; chunk: a multiple of 1024,
+ * at most 2^18 (else DWM_EINVAL).  The g pointers need 4-byte alignment only (DDP bucket views start anywhere); no byte outside
+ * [g, g + n) is read.  partials [n_blocks] (fp64) and flags [n_blocks] are caller scratch, fully overwritten.  Two launches:
+ *   out[0] = || pre_scale * g ||_2 over the whole list: every element times pre_scale, squared and summed in fp32 runs of at most
+ *            chunk / 1024 squares, the runs summed in fp64 in a fixed order (no atomics: bit-reproducible), the root rounded to fp32
+ *   out[1] = pre_scale * min(1, max_norm / (out[0] + 1e-6)), in fp32 from the fp32 out[0]; max_norm <= 0: pre_scale (no clip).
+ *            The grad_scale for dwm_adamw_multi / dwm_adamw8_multi, which then see the unscaled, clipped gradient.
+ *   out[2] = 1.0 if any ELEMENT has all exponent bits set (inf / nan; tested on the elements, not on the sum), else 0.0
+ *   out[3] = 0
+ * dwm_grad_scale_multi: g *= coef in place over the same tables (for callers with an optimizer of their own). */
+typedef struct dwm_grad_item { float* g; int64_t n; } dwm_grad_item;
+int dwm_grad_sumsq_multi(const dwm_grad_item* items, const int32_t* block_item, const int64_t* block_start, int64_t n_blocks,
+                         int64_t chunk, float pre_scale, float max_norm, double* partials, uint32_t* flags, float* out,
+                         void* stream);
+int dwm_grad_scale_multi(const dwm_grad_item* items, const int32_t* block_item, const int64_t* block_start, int64_t n_blocks,
+                         int64_t chunk, float coef, void* stream);
+
 /* Backward of dwm_groupnorm_silu / dwm_groupnorm_silu_mapped (the UNet's ResnetBlock2D / TemporalResnetBlock / TransformerModel
  * norms in the SD 2.1 training branch, src/dwm/pipelines/ctsd.py:1240-1253): x = the forward input (compact rows, through
  * img_map if given), dz = gradient of the forward OUTPUT read through dz_map (the padded grid the forward wrote, or NULL for

@@ -358,14 +358,25 @@ class CTSDTrainer:
                  max_grad_norm: Optional[float] = None, weighting_scheme: str = "logit_normal", ddp: bool = False,
                  ddp_kwargs: Optional[dict] = None, common_config: Optional[dict] = None, training_config: Optional[dict] = None,
                  reference_latent_count=0, lr_scheduler=None, ddp_comm_dtype: Optional[torch.dtype] = None,
-                 train_scheduler=None, optimizer_bits: int = 32):
+                 train_scheduler=None, optimizer_bits: int = 32, grad_conditioning: str = "torch"):
         """common_config["frame_prediction_style"] (None | "diffusion_forcing" | "ctsd") and training_config select the
         training task mix of `make_input_for_prediction`; with "diffusion_forcing" every frame draws its own timestep
         (ctsd.py:1232-1237).  optimizer_bits: 32 = train.AdamW (fp32 moments), 8 = train.AdamW8bit (block-wise 8-bit moments: the
-        reference's single-GPU recipe, docs/CtsdPipelineFaqs.md "Single GPU training")."""
+        reference's single-GPU recipe, docs/CtsdPipelineFaqs.md "Single GPU training").
+        grad_conditioning: how an optimizing step unscales, clips and checks the gradients.  "torch" (default): GradScaler.unscale_,
+        torch.nn.utils.clip_grad_norm_, GradScaler.step - three passes of torch arithmetic over every gradient.  "fused": ONE read
+        (train.grad_norm_and_coef: norm, non-finite flag, coefficient) and the coefficient handed to the AdamW kernel as its
+        grad_scale; the gradients are never rewritten, the loss scale is a train.LossScaler (GradScaler's dynamics and state dict),
+        `last_grad_norm` / `skipped_steps` are kept for logging.  One deviation from the reference's control flow, in this mode
+        only: with a clip but NO scaler a step whose gradients hold an inf / nan is skipped (with one warning) - the torch route
+        clips by a nan coefficient there and writes nan into every weight."""
         from . import train as _train
         if optimizer_bits not in (8, 32):
             raise ValueError(f"optimizer_bits: 8 or 32, got {optimizer_bits!r}")
+        if grad_conditioning not in ("torch", "fused"):
+            raise ValueError(f"grad_conditioning: 'torch' or 'fused', got {grad_conditioning!r}")
+        self.grad_conditioning = grad_conditioning
+        self.last_grad_norm, self.skipped_steps, self._warned_nonfinite = 0.0, 0, False
         self.model = model.train()
         self.wrapper = model
         self.common_config, self.training_config = dict(common_config or {}), dict(training_config or {})
@@ -405,7 +416,7 @@ class CTSDTrainer:
                 raise NotImplementedError("enable_grad_scaler with distribution_framework != 'ddp' in a distributed run "
                                           "(ShardedGradScaler / FSDP) - SURVEY.md s2")
             dev_type = next(model.parameters()).device.type
-            self.grad_scaler = torch.amp.GradScaler(dev_type)
+            self.grad_scaler = _train.LossScaler() if grad_conditioning == "fused" else torch.amp.GradScaler(dev_type)
         self.weighting_scheme = weighting_scheme
         self.reference_latent_count = reference_latent_count
         # SD 2.1 branch (ctsd.py:1240-1253): the model is the UNet -> DDPM noising, epsilon / v_prediction target
@@ -544,6 +555,28 @@ class CTSDTrainer:
         self.optimizer.load_state_dict(torch.load(os.path.join(output_path, "optimizer", f"{resume_from}.pth"),
                                                   map_location="cpu", weights_only=True))
 
+    def _fused_optimizer_step(self, scaler) -> None:
+        """the optimizing part of train_step in grad_conditioning="fused": one read of the gradients, one host sync, the AdamW
+        launch with the coefficient; nothing extra when neither a clip nor a scaler is configured"""
+        if scaler is None and self.max_grad_norm is None:
+            self.optimizer.step()
+        else:
+            from .train import grad_norm_and_coef
+            inv_scale = 1.0 if scaler is None else 1.0 / scaler.get_scale()
+            self.last_grad_norm, coef, found_inf = grad_norm_and_coef(self.model.parameters(), self.max_grad_norm, inv_scale)
+            if found_inf:
+                self.skipped_steps += 1
+                if scaler is None and not self._warned_nonfinite:
+                    import warnings
+                    warnings.warn("CTSDTrainer(grad_conditioning='fused'): non-finite gradient without a grad scaler - the optimizer "
+                                  "step is skipped (further ones silently; see skipped_steps)")
+                    self._warned_nonfinite = True
+            else:
+                self.optimizer.step(grad_scale=coef)
+            if scaler is not None:
+                scaler.update(found_inf)
+        self.optimizer.zero_grad()
+
     def train_step(self, latents: torch.Tensor, conditions: Dict[str, torch.Tensor], generator=None,
                    timestep_indices=None, noise=None, global_step: Optional[int] = None) -> torch.Tensor:
         """one call of the reference's train_step (ctsd.py:1195-1437); `global_step` defaults to the number of calls so far"""
@@ -556,7 +589,9 @@ class CTSDTrainer:
         with sync:
             loss = self.loss(latents, conditions, generator, timestep_indices, noise)
             (loss if scaler is None else scaler.scale(loss)).backward()                   # :1401-1404
-        if should_optimize:
+        if should_optimize and getattr(self, "grad_conditioning", "torch") == "fused":
+            self._fused_optimizer_step(scaler)
+        elif should_optimize:
             if self.max_grad_norm is not None:
                 if scaler is not None:
                     scaler.unscale_(self.optimizer)                                      # :1411-1413

@@ -1004,3 +1004,85 @@ class AdamW8bit(AdamW):
                     st[key] = T.dequantize_blockwise8(st[key], st.pop(key + "_absmax"), code)
             state[i] = st
         return {"state": state, "param_groups": sd["param_groups"]}
+
+
+# ------------------------------------------------------------------------------------------ gradient clip / loss scale
+def _grad_list(parameters) -> list:
+    """the gradients `AdamW.step` would read, as it reads them: `None` skipped, a non-fp32 one as `.float()`, a non-contiguous one
+    as `.contiguous()` -> [(the parameter's grad, the fp32 contiguous tensor of the same values)]"""
+    if torch.is_tensor(parameters):
+        parameters = [parameters]
+    out = []
+    for p in parameters:
+        if p.grad is None:
+            continue
+        g = p.grad if p.grad.dtype == torch.float32 else p.grad.float()
+        out.append((p.grad, g.contiguous()))
+    return out
+
+
+@torch.no_grad()
+def grad_norm_and_coef(parameters, max_norm: Optional[float] = None, inv_scale: float = 1.0):
+    """(total_norm, coef, found_inf) of the gradients of `parameters` in ONE read of them (`dwm_grad_sumsq_multi`) and one host
+    sync: total_norm = the L2 norm of inv_scale * grad over the whole list (torch.nn.utils.clip_grad_norm_'s norm after
+    GradScaler.unscale_), coef = inv_scale * min(1, max_norm / (total_norm + 1e-6)) - what `AdamW.step(grad_scale=coef)` needs to
+    see the unscaled, clipped gradient without anyone rewriting it - and found_inf = some gradient element is inf or nan
+    (GradScaler's test).  max_norm None: no clip, coef = inv_scale."""
+    gs = [g for _, g in _grad_list(parameters)]
+    total_norm, coef, found, _ = T.grad_sumsq_multi(gs, inv_scale, max_norm).tolist()
+    return total_norm, coef, found != 0.0
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm: float, inv_scale: float = 1.0) -> torch.Tensor:
+    """torch.nn.utils.clip_grad_norm_ (L2) for callers with an optimizer of their own: returns the total norm of
+    inv_scale * grad and multiplies every gradient in place by coef = inv_scale * min(1, max_norm / (norm + 1e-6)) with one launch
+    (`dwm_grad_scale_multi`); coef == 1.0 - torch multiplies by 1.0 there - launches nothing.  One host sync."""
+    pairs = _grad_list(parameters)
+    out = T.grad_sumsq_multi([g for _, g in pairs], inv_scale, max_norm)
+    coef = float(out[1])
+    if coef != 1.0:
+        T.grad_scale_multi_([g for _, g in pairs], coef)
+        for grad, g in pairs:
+            if g is not grad:                   # the kernel scaled the fp32 / contiguous copy: hand the values back
+                grad.copy_(g)
+    return out[0]
+
+
+class LossScaler:
+    """The dynamic loss scale of torch.amp.GradScaler kept on the host, for a step whose non-finite flag already is on the host
+    (`grad_norm_and_coef`): `scale(loss)` multiplies, `update(found_inf)` backs off (scale *= backoff_factor, tracker = 0) after
+    a step that found an inf / nan, otherwise counts and grows (scale *= growth_factor, tracker = 0) every `growth_interval`
+    clean steps.  The state dict has GradScaler's keys, so the two load each other's."""
+
+    def __init__(self, init_scale: float = 65536.0, growth_factor: float = 2.0, backoff_factor: float = 0.5,
+                 growth_interval: int = 2000):
+        if growth_factor <= 1.0 or not 0.0 < backoff_factor < 1.0 or growth_interval < 1:
+            raise ValueError("LossScaler: growth_factor > 1, 0 < backoff_factor < 1, growth_interval >= 1")
+        self._scale = float(torch.tensor(init_scale, dtype=torch.float32))      # GradScaler keeps the scale in fp32
+        self.growth_factor, self.backoff_factor, self.growth_interval = float(growth_factor), float(backoff_factor), int(growth_interval)
+        self._growth_tracker = 0
+
+    def scale(self, loss: torch.Tensor) -> torch.Tensor:
+        return loss * self._scale
+
+    def get_scale(self) -> float:
+        return self._scale
+
+    def update(self, found_inf: bool) -> None:
+        if found_inf:
+            self._scale, self._growth_tracker = self._scale * self.backoff_factor, 0
+        else:
+            self._growth_tracker += 1
+            if self._growth_tracker == self.growth_interval:
+                self._scale, self._growth_tracker = self._scale * self.growth_factor, 0
+        self._scale = float(torch.tensor(self._scale, dtype=torch.float32))
+
+    def state_dict(self) -> dict:
+        return {"scale": self._scale, "growth_factor": self.growth_factor, "backoff_factor": self.backoff_factor,
+                "growth_interval": self.growth_interval, "_growth_tracker": self._growth_tracker}
+
+    def load_state_dict(self, state_dict: dict) -> None:
+        self._scale = float(state_dict["scale"])
+        self.growth_factor, self.backoff_factor = float(state_dict["growth_factor"]), float(state_dict["backoff_factor"])
+        self.growth_interval, self._growth_tracker = int(state_dict["growth_interval"]), int(state_dict["_growth_tracker"])

@@ -269,6 +269,68 @@ def adamw8_multi_(ps, gs, mqs, mas, vqs, vas, shadows, *, lr: float, beta1: floa
           beta2, eps, weight_decay, 1.0 - beta1 ** step, 1.0 - beta2 ** step, grad_scale)
 
 
+# ---- gradient norm / clip coefficient / non-finite check in one read (gradnorm.hip)
+GRAD_CHUNK = 1 << 16                     # elements per workgroup of dwm_grad_sumsq_multi / dwm_grad_scale_multi
+GRAD_SUMSQ_E = GRAD_CHUNK // 1024        # squares one fp32 accumulator of grad_sumsq_multi_kernel receives per chunk, at most
+# (device, tuple of numels) -> (block_item, block_start, partials fp64, flags) on the device.  A cache of its own: _ADAMW_BLOCKS holds
+# the two lists of an optimizer, a third key there would evict one of them every step.  The scratch buffers are reused by every call
+# with this key, so calls on one list belong on one stream.
+_GRAD_TABLES: dict = {}
+
+
+def _grad_tables(dev: torch.device, numels: tuple):
+    key = (dev.index, numels)
+    tab = _GRAD_TABLES.get(key)
+    if tab is None:
+        bi, bs = [], []
+        for i, n in enumerate(numels):
+            nb = (n + GRAD_CHUNK - 1) // GRAD_CHUNK
+            bi.append(torch.full((nb,), i, dtype=torch.int32))
+            bs.append(torch.arange(nb, dtype=torch.int64) * GRAD_CHUNK)
+        while len(_GRAD_TABLES) >= 2:
+            _GRAD_TABLES.pop(next(iter(_GRAD_TABLES)))
+        bi = torch.cat(bi).to(dev)
+        tab = _GRAD_TABLES[key] = (bi, torch.cat(bs).to(dev), torch.empty(bi.numel(), dtype=torch.float64, device=dev),
+                                   torch.empty(bi.numel(), dtype=torch.int32, device=dev))
+    return tab
+
+
+def _grad_items(gs, what: str):
+    """(device, non-empty entries, their dwm_grad_item rows on the device) of a gradient list"""
+    gs = [g for g in gs if g.numel() > 0]
+    if not gs:
+        return None, gs, None
+    dev = gs[0].device
+    for g in gs:
+        if g.dtype != torch.float32 or not g.is_contiguous() or g.device != dev or not g.is_cuda or g.data_ptr() % 4:
+            raise RuntimeError(f"{what}: fp32 contiguous tensors on one HIP device expected (there is no CPU fallback)")
+    items = torch.tensor([(g.data_ptr(), g.numel()) for g in gs], dtype=torch.int64).to(dev, non_blocking=True)   # dwm_grad_item[n]
+    return dev, gs, items
+
+
+def grad_sumsq_multi(gs, pre_scale: float = 1.0, max_norm: Optional[float] = None) -> torch.Tensor:
+    """dwm_grad_sumsq_multi over a list of fp32 tensors (any 4-byte aligned views): device tensor [4] = (|| pre_scale * g ||_2,
+    coef = pre_scale * min(1, max_norm / (norm + 1e-6)), 1.0 if any element is inf / nan else 0.0, 0).  max_norm None or <= 0: no
+    clip, coef = pre_scale.  Empty tensors are dropped; an empty list gives (0, pre_scale, 0, 0) without a launch."""
+    dev, gs, items = _grad_items(gs, "grad_sumsq_multi")
+    if not gs:
+        return torch.tensor([0.0, pre_scale, 0.0, 0.0], dtype=torch.float32)
+    bi, bs, partials, flags = _grad_tables(dev, tuple(g.numel() for g in gs))
+    out = torch.empty(4, dtype=torch.float32, device=dev)
+    _call("dwm_grad_sumsq_multi", _p(items), _p(bi), _p(bs), bi.numel(), GRAD_CHUNK, pre_scale, 0.0 if max_norm is None else max_norm,
+          _p(partials), _p(flags), _p(out))
+    return out
+
+
+def grad_scale_multi_(gs, coef: float) -> None:
+    """dwm_grad_scale_multi: g *= coef in place for every tensor of the list, one launch"""
+    dev, gs, items = _grad_items(gs, "grad_scale_multi_")
+    if not gs:
+        return
+    bi, bs, _, _ = _grad_tables(dev, tuple(g.numel() for g in gs))
+    _call("dwm_grad_scale_multi", _p(items), _p(bi), _p(bs), bi.numel(), GRAD_CHUNK, coef)
+
+
 # ------------------------------------------------------------------------------------------ composites
 def linear_dgrad(dy: torch.Tensor, w_t: torch.Tensor, out: Optional[torch.Tensor] = None, **epi) -> torch.Tensor:
     """dX [M, K] = dY [M, N] @ W [N, K], with W^T [K, N] given (the GEMM contracts over the columns of
