@@ -1,7 +1,7 @@
 """GPU leg (`-m gpu`): parity of the HIP path (through the C ABI) against the oracle /
 plain fp32 torch references, on seeded inputs.  Tolerances follow BASELINE.json's
 north_star: <= 2e-2 relative (Frobenius) for the bf16 path against the fp32 reference;
-individual kernels are held to a much tighter bound (bf16 output rounding, 2^-9).
+individual kernels are held to a much tighter bound (bf16 output rounding, 2^-8 relative at most).
 Every measured error is appended to gpurun_out/gpu_parity.log."""
 import json
 import os
@@ -16,7 +16,7 @@ from tests.common import GOLDEN, rel_err, small_config, small_inputs, to_dev
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 bf16 = torch.bfloat16
-TOL_KERNEL = 6e-3       # one bf16 rounding of the output (2^-9 max, ~1.1e-3 rms) plus fp32 accumulation order
+TOL_KERNEL = 6e-3       # one bf16 rounding of the output (2^-8 relative max: half an ulp at a binade's start; ~1.1e-3 rms) plus fp32 accumulation order
 TOL_MODEL = 2e-2        # BASELINE.json north_star, bf16
 
 
