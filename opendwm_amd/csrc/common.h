@@ -177,6 +177,22 @@ DWM_DEVINL uint32_t fmod_u(uint32_t n, const FastDiv& f) { return n - fdiv(n, f)
 
 static inline bool dwm_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
+// ---- tensor lists (dwm_adamw_multi, dwm_adamw8_multi, dwm_grad_sumsq_multi, dwm_grad_scale_multi): workgroup b owns elements
+// [i0, i1) = [block_start[b], min(block_start[b] + chunk, n)) of tensor block_item[b].  Item: any of the item structs (field `n`).
+template <typename Item>
+DWM_DEVINL Item dwm_list_chunk(const Item* __restrict__ items, const int32_t* __restrict__ block_item,
+                               const int64_t* __restrict__ block_start, int64_t chunk, int64_t& i0, int64_t& i1) {
+    const Item it = items[block_item[blockIdx.x]];
+    i0 = block_start[blockIdx.x];
+    i1 = i0 + chunk < it.n ? i0 + chunk : it.n;
+    return it;
+}
+// what every entry point of a tensor list refuses (each adds its own conditions on chunk and on its other arguments)
+static inline bool dwm_bad_list_tables(const void* items, const int32_t* block_item, const int64_t* block_start, int64_t n_blocks,
+                                       int64_t chunk) {
+    return !items || !block_item || !block_start || n_blocks <= 0 || n_blocks >= (1ll << 31) || chunk <= 0;
+}
+
 // ---- host-side launch helpers.  Their caches are per device and idempotent (a lost race repeats a harmless call), so any thread
 // may launch on any device; the steady-state cost is one hipGetDevice and one atomic load.
 // Raises the dynamic-LDS limit of Kernel to `bytes`, once per (kernel, current device; devices >= 64: every time).  Keyed on the

@@ -50,9 +50,8 @@ grad_sumsq_multi_kernel(const dwm_grad_item* __restrict__ items, const int32_t* 
                         uint32_t* __restrict__ flags) {
     __shared__ double wsum[GN_THREADS / 64];
     __shared__ uint32_t wflag[GN_THREADS / 64];
-    const dwm_grad_item it = items[block_item[blockIdx.x]];
-    const int64_t i0 = block_start[blockIdx.x];
-    const int64_t i1 = i0 + chunk < it.n ? i0 + chunk : it.n;
+    int64_t i0, i1;
+    const dwm_grad_item it = dwm_list_chunk(items, block_item, block_start, chunk, i0, i1);
     const int t = threadIdx.x;
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, edge = 0.f;
     uint32_t bad = 0;
@@ -144,9 +143,8 @@ grad_finish_kernel(const double* __restrict__ partials, const uint32_t* __restri
 __global__ void __launch_bounds__(GN_THREADS)
 grad_scale_multi_kernel(const dwm_grad_item* __restrict__ items, const int32_t* __restrict__ block_item,
                         const int64_t* __restrict__ block_start, int64_t chunk, float coef) {
-    const dwm_grad_item it = items[block_item[blockIdx.x]];
-    const int64_t i0 = block_start[blockIdx.x];
-    const int64_t i1 = i0 + chunk < it.n ? i0 + chunk : it.n;
+    int64_t i0, i1;
+    const dwm_grad_item it = dwm_list_chunk(items, block_item, block_start, chunk, i0, i1);
     if (i0 >= i1) return;
     const int t = threadIdx.x;
     gn_gf32* const g = (gn_gf32*)it.g;
@@ -172,8 +170,7 @@ grad_scale_multi_kernel(const dwm_grad_item* __restrict__ items, const int32_t* 
 // chunk: a multiple of 1024 (one float4 per lane and round) of at most 2^18, so that one fp32 accumulator receives at most 256 squares
 static bool gn_bad_tables(const dwm_grad_item* items, const int32_t* block_item, const int64_t* block_start, int64_t n_blocks,
                           int64_t chunk) {
-    return !items || !block_item || !block_start || n_blocks <= 0 || n_blocks >= (1ll << 31) || chunk <= 0 || chunk % 1024 != 0 ||
-           chunk > (1ll << 18);
+    return dwm_bad_list_tables(items, block_item, block_start, n_blocks, chunk) || chunk % 1024 != 0 || chunk > (1ll << 18);
 }
 
 extern "C" int dwm_grad_sumsq_multi(const dwm_grad_item* items, const int32_t* block_item, const int64_t* block_start,

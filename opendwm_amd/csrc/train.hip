@@ -439,16 +439,29 @@ rmsnorm_heads_bwd_kernel(const bf16_t* __restrict__ y, int64_t ldy, const float*
 // ---------------------------------------------------------------------------------- optimizer / casts
 // AdamW (decoupled weight decay, torch.optim.AdamW semantics) on fp32 master parameters; refreshes
 // the bf16 compute copy in the same pass.
+struct AdamwHyper { float lr, b1, b2, eps, wd, bc1, bc2, gscale; };
+
+// One element: the new p; m and v go in as the old moments and come out as the new ones.  The callers read g, p, m, v in that order
+// before the call: which product of a moment update the compiler fuses into the fma follows the order of the loads, and the last bit
+// of m and v with it.
+DWM_DEVINL float adamw_update(float p, float g, float& m, float& v, const AdamwHyper& h) {
+    const float gi = g * h.gscale;
+    float pi = p * (1.f - h.lr * h.wd);
+    m = h.b1 * m + (1.f - h.b1) * gi;
+    v = h.b2 * v + (1.f - h.b2) * gi * gi;
+    pi -= h.lr * (m / h.bc1) / (sqrtf(v / h.bc2) + h.eps);
+    return pi;
+}
+
 __global__ void __launch_bounds__(256)
 adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
              bf16_t* __restrict__ pb, int64_t n, float lr, float b1, float b2, float eps, float wd,
              float bc1, float bc2, float gscale) {
+    const AdamwHyper h{lr, b1, b2, eps, wd, bc1, bc2, gscale};
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const float gi = g[i] * gscale;
-        float pi = p[i] * (1.f - lr * wd);
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        pi -= lr * (mi / bc1) / (sqrtf(vi / bc2) + eps);
+        const float gi = g[i], p0 = p[i];
+        float mi = m[i], vi = v[i];
+        const float pi = adamw_update(p0, gi, mi, vi, h);
         p[i] = pi; m[i] = mi; v[i] = vi;
         if (pb) pb[i] = f32_to_bf16(pi);
     }
@@ -460,20 +473,18 @@ __global__ void __launch_bounds__(256)
 adamw_multi_kernel(const dwm_adamw_item* __restrict__ items, const int32_t* __restrict__ block_item,
                    const int64_t* __restrict__ block_start, int64_t chunk, float lr, float b1, float b2, float eps, float wd,
                    float bc1, float bc2, float gscale) {
-    const dwm_adamw_item it = items[block_item[blockIdx.x]];
-    const int64_t i0 = block_start[blockIdx.x];
-    const int64_t i1 = i0 + chunk < it.n ? i0 + chunk : it.n;
+    int64_t i0, i1;
+    const dwm_adamw_item it = dwm_list_chunk(items, block_item, block_start, chunk, i0, i1);
+    const AdamwHyper h{lr, b1, b2, eps, wd, bc1, bc2, gscale};
     float* __restrict__ p = it.p;
     const float* __restrict__ g = it.g;
     float* __restrict__ m = it.m;
     float* __restrict__ v = it.v;
     bf16_t* __restrict__ pb = (bf16_t*)it.p_bf16;
     for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
-        const float gi = g[i] * gscale;
-        float pi = p[i] * (1.f - lr * wd);
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        pi -= lr * (mi / bc1) / (sqrtf(vi / bc2) + eps);
+        const float gi = g[i], p0 = p[i];
+        float mi = m[i], vi = v[i];
+        const float pi = adamw_update(p0, gi, mi, vi, h);
         p[i] = pi; m[i] = mi; v[i] = vi;
         if (pb) pb[i] = f32_to_bf16(pi);
     }
@@ -614,9 +625,9 @@ adamw8_multi_kernel(const dwm_adamw8_item* __restrict__ items, const int32_t* __
     q8_stage_table(code_m, tab_m);
     q8_stage_table(code_v, tab_v);
     __syncthreads();
-    const dwm_adamw8_item it = items[block_item[blockIdx.x]];
-    const int64_t i0 = block_start[blockIdx.x];
-    const int64_t i1 = i0 + chunk < it.n ? i0 + chunk : it.n;
+    int64_t i0, i1;
+    const dwm_adamw8_item it = dwm_list_chunk(items, block_item, block_start, chunk, i0, i1);
+    const AdamwHyper h{lr, b1, b2, eps, wd, bc1, bc2, gscale};
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* __restrict__ p = it.p;
     const float* __restrict__ g = it.g;
@@ -636,12 +647,9 @@ adamw8_multi_kernel(const dwm_adamw8_item* __restrict__ items, const int32_t* __
         float am = 0.f, av = 0.f;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float gj = gi[j] * gscale;
-            float pj = pi[j] * (1.f - lr * wd);
-            mi[j] = b1 * (tab_m[(wm >> (8 * j)) & 255u] * sm) + (1.f - b1) * gj;
-            vi[j] = b2 * (tab_v[(wv >> (8 * j)) & 255u] * sv) + (1.f - b2) * gj * gj;
-            pj -= lr * (mi[j] / bc1) / (sqrtf(vi[j] / bc2) + eps);
-            pi[j] = pj;
+            mi[j] = tab_m[(wm >> (8 * j)) & 255u] * sm;
+            vi[j] = tab_v[(wv >> (8 * j)) & 255u] * sv;
+            pi[j] = adamw_update(pi[j], gi[j], mi[j], vi[j], h);
             am = fmaxf(am, fabsf(mi[j]));
             av = fmaxf(av, vi[j]);
         }
@@ -849,8 +857,8 @@ extern "C" int dwm_adamw(float* p, const float* g, float* m, float* v, void* p_b
 extern "C" int dwm_adamw_multi(const dwm_adamw_item* items, const int32_t* block_item, const int64_t* block_start, int64_t n_blocks,
                                int64_t chunk, float lr, float beta1, float beta2, float eps, float weight_decay, float bias_corr1,
                                float bias_corr2, float grad_scale, void* stream) {
-    if (!items || !block_item || !block_start || n_blocks <= 0 || n_blocks >= (1ll << 31) || chunk <= 0 || bias_corr1 <= 0.f ||
-        bias_corr2 <= 0.f) return DWM_EINVAL;
+    if (dwm_bad_list_tables(items, block_item, block_start, n_blocks, chunk) || bias_corr1 <= 0.f || bias_corr2 <= 0.f)
+        return DWM_EINVAL;
     hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, items, block_item, block_start,
                        chunk, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale);
     return dwm_launch_status();
@@ -876,8 +884,8 @@ extern "C" int dwm_adamw8_multi(const dwm_adamw8_item* items, const int32_t* blo
                                 int64_t n_blocks, int64_t chunk, const float* code_m, const float* code_v, float lr, float beta1,
                                 float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2, float grad_scale,
                                 void* stream) {
-    if (!items || !block_item || !block_start || !code_m || !code_v || n_blocks <= 0 || n_blocks >= (1ll << 31) || chunk <= 0 ||
-        chunk % Q8_BLOCK != 0 || bias_corr1 <= 0.f || bias_corr2 <= 0.f) return DWM_EINVAL;
+    if (dwm_bad_list_tables(items, block_item, block_start, n_blocks, chunk) || !code_m || !code_v || chunk % Q8_BLOCK != 0 ||
+        bias_corr1 <= 0.f || bias_corr2 <= 0.f) return DWM_EINVAL;
     hipLaunchKernelGGL(adamw8_multi_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, items, block_item,
                        block_start, chunk, code_m, code_v, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale);
     return dwm_launch_status();

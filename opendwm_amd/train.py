@@ -825,9 +825,18 @@ def forward_train(model, sample, timestep, encoder_hidden_states, pooled_project
 
 
 # ------------------------------------------------------------------------------------------ optimizer
+def _fp32_grad(p) -> Optional[torch.Tensor]:
+    """the gradient of p as the optimizer step and the gradient norm read it: `None` if there is none, else its values as an fp32
+    contiguous tensor - `p.grad` itself where it is one, a `.float()` / `.contiguous()` copy otherwise"""
+    g = p.grad
+    if g is None:
+        return None
+    return (g if g.dtype == torch.float32 else g.float()).contiguous()
+
+
 class AdamW(torch.optim.Optimizer):
-    """torch.optim.AdamW semantics with the update done by the HIP kernel (`dwm_adamw`), which also refreshes the bf16
-    compute shadows of blocks.STORE.
+    """torch.optim.AdamW semantics with the update done by the HIP kernel (`dwm_adamw_multi`, one launch per step count), which
+    also refreshes the bf16 compute shadows of blocks.STORE.
 
     It IS a torch.optim.Optimizer: parameter groups, the (sparse) per-parameter state with its own step count, and the
     state-dict format are torch's bookkeeping, so `optimizer/<step>.pth` files interchange with the reference's
@@ -851,43 +860,61 @@ class AdamW(torch.optim.Optimizer):
         """largest per-parameter step count"""
         return max((int(float(st["step"])) for st in self.state.values() if "step" in st), default=0)
 
+    def _init_state(self, p) -> dict:
+        """fresh state of p: step 0, zero fp32 moments"""
+        st = self.state[p]
+        st["step"] = torch.tensor(0.0)
+        st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        return st
+
     @torch.no_grad()
     def step(self, closure=None, grad_scale: float = 1.0):
+        """the step of `AdamW` and of `AdamW8bit`: a parameter whose `exp_avg` is uint8 goes to the `dwm_adamw8_multi` batch of its
+        step count, every other one to the `dwm_adamw_multi` batch; per group the 8-bit batches are launched first"""
+        name = type(self).__name__
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         for group in self.param_groups:
             if group.get("amsgrad") or group.get("maximize"):
-                raise NotImplementedError("AdamW: amsgrad / maximize")
+                raise NotImplementedError(f"{name}: amsgrad / maximize")
             b1, b2 = group["betas"]
-            batches: dict = {}                  # step count -> lists for ONE dwm_adamw_multi launch (normally a single batch)
+            hyper = dict(lr=float(group["lr"]), beta1=b1, beta2=b2, eps=group["eps"], weight_decay=group["weight_decay"],
+                         grad_scale=grad_scale)
+            batches8: dict = {}                 # step count -> lists for ONE dwm_adamw8_multi launch (normally a single batch)
+            batches32: dict = {}                # the same for the fp32-moment tensors (dwm_adamw_multi)
             for p in group["params"]:
-                if p.grad is None:              # frozen, or unused in this step: no state, no step (as torch)
+                g = _fp32_grad(p)
+                if g is None:                   # frozen, or unused in this step: no state, no step (as torch)
                     continue
                 if p.dtype != torch.float32:
-                    raise RuntimeError("AdamW: fp32 master parameters expected")
+                    raise RuntimeError(f"{name}: fp32 master parameters expected")
                 st = self.state[p]
                 if len(st) == 0:
-                    st["step"] = torch.tensor(0.0)
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st = self._init_state(p)
                 st["step"] += 1
-                g = p.grad if p.grad.dtype == torch.float32 else p.grad.float()
                 shadow = STORE.bf(p) if (p.is_cuda and p.numel() % 4 == 0 and p.is_contiguous()) else None
                 if shadow is None:
                     STORE._shadow.pop(id(p), None)      # re-cast on next use
-                step = int(st["step"].item())
-                if p.is_contiguous() and st["exp_avg"].is_contiguous() and st["exp_avg_sq"].is_contiguous():
-                    b = batches.setdefault(step, ([], [], [], [], []))
-                    for lst, t in zip(b, (p.data, g.contiguous(), st["exp_avg"], st["exp_avg_sq"], shadow)):
-                        lst.append(t)
+                if st["exp_avg"].dtype == torch.uint8:
+                    batches, row = batches8, (p.data, g, st["exp_avg"], st["exp_avg_absmax"], st["exp_avg_sq"],
+                                              st["exp_avg_sq_absmax"], shadow)
+                elif p.is_contiguous() and st["exp_avg"].is_contiguous() and st["exp_avg_sq"].is_contiguous():
+                    batches, row = batches32, (p.data, g, st["exp_avg"], st["exp_avg_sq"], shadow)
                 else:
-                    T.adamw_(p.data, g.contiguous(), st["exp_avg"], st["exp_avg_sq"], shadow, lr=float(group["lr"]), beta1=b1, beta2=b2,
-                             eps=group["eps"], weight_decay=group["weight_decay"], step=step, grad_scale=grad_scale)
-            for step, (ps, gs, ms, vs, shs) in batches.items():
-                T.adamw_multi_(ps, gs, ms, vs, shs, lr=float(group["lr"]), beta1=b1, beta2=b2, eps=group["eps"],
-                               weight_decay=group["weight_decay"], step=step, grad_scale=grad_scale)
+                    raise RuntimeError(f"{name}: the parameter of shape {tuple(p.shape)} or its moments are not contiguous "
+                                       "(the kernels take contiguous tensors; there is no strided path)")
+                step = int(st["step"].item())
+                if step not in batches:
+                    batches[step] = tuple([] for _ in row)
+                for lst, t in zip(batches[step], row):
+                    lst.append(t)
+            for step, lists in batches8.items():
+                T.adamw8_multi_(*lists, step=step, **hyper)
+            for step, lists in batches32.items():
+                T.adamw_multi_(*lists, step=step, **hyper)
         STORE.bump(keep_shadows=True)
         return loss
 
@@ -898,8 +925,8 @@ class AdamW8bit(AdamW):
     slot the reference's docs/CtsdPipelineFaqs.md ("Single GPU training", step 2) gives to `bitsandbytes.optim.Adam8bit`.
 
     State per quantised parameter: `step`, `exp_avg` (uint8, the parameter's shape), `exp_avg_absmax` (fp32 [ceil(n / 256)]),
-    `exp_avg_sq`, `exp_avg_sq_absmax`.  Parameters of fewer than `min_8bit_size` elements and non-contiguous ones keep fp32
-    moments and take `AdamW`'s path unchanged.  The parameter update is computed from the fresh fp32 moments; quantisation only
+    `exp_avg_sq`, `exp_avg_sq_absmax`.  Parameters of fewer than `min_8bit_size` elements keep fp32 moments; `AdamW.step`, the only
+    `step`, sorts by the dtype of `exp_avg`.  The parameter update is computed from the fresh fp32 moments; quantisation only
     affects what the next step starts from.
 
     `load_state_dict` takes its own files and fp32-moment files (torch.optim.AdamW's, the reference's, `AdamW`'s: quantised on
@@ -914,63 +941,15 @@ class AdamW8bit(AdamW):
 
     def _init_state(self, p) -> dict:
         """fresh state of p: zero moments (8-bit: the code of 0.0 everywhere, scales 0)"""
+        if not self._wants_8bit(p):
+            return super()._init_state(p)
         st = self.state[p]
         st["step"] = torch.tensor(0.0)
-        if self._wants_8bit(p):
-            nb = quant8.n_blocks(p.numel())
-            for key, signed in (("exp_avg", True), ("exp_avg_sq", False)):
-                st[key] = torch.full(p.shape, quant8.zero_code(signed), dtype=torch.uint8, device=p.device)
-                st[key + "_absmax"] = torch.zeros(nb, dtype=torch.float32, device=p.device)
-        else:
-            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        nb = quant8.n_blocks(p.numel())
+        for key, signed in (("exp_avg", True), ("exp_avg_sq", False)):
+            st[key] = torch.full(p.shape, quant8.zero_code(signed), dtype=torch.uint8, device=p.device)
+            st[key + "_absmax"] = torch.zeros(nb, dtype=torch.float32, device=p.device)
         return st
-
-    @torch.no_grad()
-    def step(self, closure=None, grad_scale: float = 1.0):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        for group in self.param_groups:
-            if group.get("amsgrad") or group.get("maximize"):
-                raise NotImplementedError("AdamW8bit: amsgrad / maximize")
-            b1, b2 = group["betas"]
-            hyper = dict(lr=float(group["lr"]), beta1=b1, beta2=b2, eps=group["eps"], weight_decay=group["weight_decay"],
-                         grad_scale=grad_scale)
-            batches8: dict = {}                 # step count -> lists for ONE dwm_adamw8_multi launch (normally a single batch)
-            batches32: dict = {}                # the same for the fp32-moment tensors (dwm_adamw_multi)
-            for p in group["params"]:
-                if p.grad is None:              # frozen, or unused in this step: no state, no step (as torch)
-                    continue
-                if p.dtype != torch.float32:
-                    raise RuntimeError("AdamW8bit: fp32 master parameters expected")
-                st = self.state[p]
-                if len(st) == 0:
-                    st = self._init_state(p)
-                st["step"] += 1
-                g = p.grad if p.grad.dtype == torch.float32 else p.grad.float()
-                shadow = STORE.bf(p) if (p.is_cuda and p.numel() % 4 == 0 and p.is_contiguous()) else None
-                if shadow is None:
-                    STORE._shadow.pop(id(p), None)      # re-cast on next use
-                step = int(st["step"].item())
-                if st["exp_avg"].dtype == torch.uint8:
-                    b = batches8.setdefault(step, ([], [], [], [], [], [], []))
-                    for lst, t in zip(b, (p.data, g.contiguous(), st["exp_avg"], st["exp_avg_absmax"], st["exp_avg_sq"],
-                                          st["exp_avg_sq_absmax"], shadow)):
-                        lst.append(t)
-                elif p.is_contiguous() and st["exp_avg"].is_contiguous() and st["exp_avg_sq"].is_contiguous():
-                    b = batches32.setdefault(step, ([], [], [], [], []))
-                    for lst, t in zip(b, (p.data, g.contiguous(), st["exp_avg"], st["exp_avg_sq"], shadow)):
-                        lst.append(t)
-                else:
-                    T.adamw_(p.data, g.contiguous(), st["exp_avg"], st["exp_avg_sq"], shadow, step=step, **hyper)
-            for step, lists in batches8.items():
-                T.adamw8_multi_(*lists, step=step, **hyper)
-            for step, lists in batches32.items():
-                T.adamw_multi_(*lists, step=step, **hyper)
-        STORE.bump(keep_shadows=True)
-        return loss
 
     @torch.no_grad()
     def load_state_dict(self, state_dict) -> None:
@@ -1008,17 +987,10 @@ class AdamW8bit(AdamW):
 
 # ------------------------------------------------------------------------------------------ gradient clip / loss scale
 def _grad_list(parameters) -> list:
-    """the gradients `AdamW.step` would read, as it reads them: `None` skipped, a non-fp32 one as `.float()`, a non-contiguous one
-    as `.contiguous()` -> [(the parameter's grad, the fp32 contiguous tensor of the same values)]"""
+    """[(the parameter's grad, `_fp32_grad` of it)] of the parameters that have a gradient: what `AdamW.step` reads"""
     if torch.is_tensor(parameters):
         parameters = [parameters]
-    out = []
-    for p in parameters:
-        if p.grad is None:
-            continue
-        g = p.grad if p.grad.dtype == torch.float32 else p.grad.float()
-        out.append((p.grad, g.contiguous()))
-    return out
+    return [(p.grad, _fp32_grad(p)) for p in parameters if p.grad is not None]
 
 
 @torch.no_grad()

@@ -163,33 +163,64 @@ def rmsnorm_heads_bwd_(y: torch.Tensor, rinv: torch.Tensor, w_expanded: torch.Te
     return dy
 
 
+# ---- tensor lists: AdamW, 8-bit AdamW and the gradient norm share one scheme.  A list of tensors is cut into chunks of `chunk` elements,
+# one workgroup per chunk; the kernels get an item array (one struct of pointers and the element count per tensor) and two block tables.
+ADAMW_CHUNK = 1 << 16            # elements per workgroup of the multi-tensor AdamW (a multiple of the 8-bit block of 256)
+GRAD_CHUNK = 1 << 16             # elements per workgroup of dwm_grad_sumsq_multi / dwm_grad_scale_multi
+GRAD_SUMSQ_E = GRAD_CHUNK // 1024        # squares one fp32 accumulator of grad_sumsq_multi_kernel receives per chunk, at most
+
+
+class _BlockTables:
+    """(block_item int32, block_start int64) of a tensor list on its device: ceil(n / chunk) workgroups per tensor, in order"""
+    def __init__(self, dev: torch.device, chunk: int, numels: tuple):
+        bi, bs = [], []
+        for i, n in enumerate(numels):
+            nb = (n + chunk - 1) // chunk
+            bi.append(torch.full((nb,), i, dtype=torch.int32))
+            bs.append(torch.arange(nb, dtype=torch.int64) * chunk)
+        self.block_item, self.block_start, self._scratch = torch.cat(bi).to(dev), torch.cat(bs).to(dev), None
+
+    def grad_scratch(self):
+        """(partials fp64, flags int32), one per block, for dwm_grad_sumsq_multi: allocated on first use and reused by every call on
+        this list, so calls on one list belong on one stream"""
+        if self._scratch is None:
+            self._scratch = (torch.empty_like(self.block_item, dtype=torch.float64), torch.empty_like(self.block_item))
+        return self._scratch
+
+
+# (device index, chunk, tuple of numels) -> _BlockTables, least recently used first.  Four entries: the fp32 list of an optimizer, its
+# 8-bit list, the gradient list (one entry with either where the numels are the same) and one spare.
+_BLOCK_TABLES: dict = {}
+
+
+def _block_tables(dev: torch.device, chunk: int, numels: tuple) -> _BlockTables:
+    key = (dev.index, chunk, numels)
+    tab = _BLOCK_TABLES.pop(key, None)                # a hit goes back in as the most recent
+    if tab is None:
+        while len(_BLOCK_TABLES) >= 4:
+            _BLOCK_TABLES.pop(next(iter(_BLOCK_TABLES)))
+        tab = _BlockTables(dev, chunk, numels)
+    _BLOCK_TABLES[key] = tab
+    return tab
+
+
+def _items(rows, dev: torch.device) -> torch.Tensor:
+    """equal-length rows of integers (the pointers of one tensor's item struct, its element count last) -> the item array on `dev`"""
+    return torch.tensor(rows, dtype=torch.int64).to(dev, non_blocking=True)
+
+
+def _adamw_scalars(lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, step: int, grad_scale: float) -> tuple:
+    """the eight trailing float arguments of dwm_adamw / dwm_adamw_multi / dwm_adamw8_multi (bias corrections from `step`)"""
+    return lr, beta1, beta2, eps, weight_decay, 1.0 - beta1 ** step, 1.0 - beta2 ** step, grad_scale
+
+
 def adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, p_bf16: Optional[torch.Tensor], *,
            lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, step: int, grad_scale: float = 1.0) -> None:
     for t in (p, g, m, v):
         if t.dtype != torch.float32 or not t.is_contiguous():
             raise RuntimeError("adamw_: fp32 contiguous tensors expected")
-    _call("dwm_adamw", _p(p), _p(g), _p(m), _p(v), _p(p_bf16), p.numel(), lr, beta1, beta2, eps, weight_decay,
-          1.0 - beta1 ** step, 1.0 - beta2 ** step, grad_scale)
-
-
-ADAMW_CHUNK = 1 << 16            # elements per workgroup of the multi-tensor AdamW (a multiple of the 8-bit block of 256)
-_ADAMW_BLOCKS: dict = {}         # (device, tuple of numels) -> (block_item, block_start) on the device: static per parameter list
-
-
-def _adamw_blocks(dev: torch.device, numels: tuple):
-    """the cached (block_item, block_start) tables of a parameter list: ceil(n / ADAMW_CHUNK) workgroups per tensor"""
-    key = (dev.index, numels)
-    tab = _ADAMW_BLOCKS.get(key)
-    if tab is None:
-        bi, bs = [], []
-        for i, n in enumerate(numels):
-            nb = (n + ADAMW_CHUNK - 1) // ADAMW_CHUNK
-            bi.append(torch.full((nb,), i, dtype=torch.int32))
-            bs.append(torch.arange(nb, dtype=torch.int64) * ADAMW_CHUNK)
-        while len(_ADAMW_BLOCKS) >= 2:                    # an optimizer has at most two lists (fp32 and 8-bit moments)
-            _ADAMW_BLOCKS.pop(next(iter(_ADAMW_BLOCKS)))
-        tab = _ADAMW_BLOCKS[key] = (torch.cat(bi).to(dev), torch.cat(bs).to(dev))
-    return tab
+    _call("dwm_adamw", _p(p), _p(g), _p(m), _p(v), _p(p_bf16), p.numel(),
+          *_adamw_scalars(lr, beta1, beta2, eps, weight_decay, step, grad_scale))
 
 
 def adamw_multi_(ps, gs, ms, vs, shadows, *, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, step: int,
@@ -205,10 +236,10 @@ def adamw_multi_(ps, gs, ms, vs, shadows, *, lr: float, beta1: float, beta2: flo
             if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel() or t.device != dev:
                 raise RuntimeError("adamw_multi_: fp32 contiguous tensors of one shape on one device expected")
         rows.append((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), 0 if sh is None else sh.data_ptr(), p.numel()))
-    items = torch.tensor(rows, dtype=torch.int64).to(dev, non_blocking=True)          # [n, 6] = dwm_adamw_item[n]
-    tab = _adamw_blocks(dev, tuple(r[5] for r in rows))
-    _call("dwm_adamw_multi", _p(items), _p(tab[0]), _p(tab[1]), tab[0].numel(), ADAMW_CHUNK, lr, beta1, beta2, eps,
-          weight_decay, 1.0 - beta1 ** step, 1.0 - beta2 ** step, grad_scale)
+    items = _items(rows, dev)                                                         # [n, 6] = dwm_adamw_item[n]
+    tab = _block_tables(dev, ADAMW_CHUNK, tuple(r[-1] for r in rows))
+    _call("dwm_adamw_multi", _p(items), _p(tab.block_item), _p(tab.block_start), tab.block_item.numel(), ADAMW_CHUNK,
+          *_adamw_scalars(lr, beta1, beta2, eps, weight_decay, step, grad_scale))
 
 
 # ---- block-wise 8-bit optimizer state (opendwm_amd.quant8: value = code[q] * absmax[block of 256])
@@ -262,73 +293,47 @@ def adamw8_multi_(ps, gs, mqs, mas, vqs, vas, shadows, *, lr: float, beta1: floa
         _chk_q8(vq, va, p.numel(), dev, "adamw8_multi_")
         rows.append((p.data_ptr(), g.data_ptr(), mq.data_ptr(), ma.data_ptr(), vq.data_ptr(), va.data_ptr(),
                      0 if sh is None else sh.data_ptr(), p.numel()))
-    items = torch.tensor(rows, dtype=torch.int64).to(dev, non_blocking=True)          # [n, 8] = dwm_adamw8_item[n]
-    tab = _adamw_blocks(dev, tuple(r[7] for r in rows))
+    items = _items(rows, dev)                                                         # [n, 8] = dwm_adamw8_item[n]
+    tab = _block_tables(dev, ADAMW_CHUNK, tuple(r[-1] for r in rows))
     code_m, code_v = quant8.device_codes(dev)
-    _call("dwm_adamw8_multi", _p(items), _p(tab[0]), _p(tab[1]), tab[0].numel(), ADAMW_CHUNK, _p(code_m), _p(code_v), lr, beta1,
-          beta2, eps, weight_decay, 1.0 - beta1 ** step, 1.0 - beta2 ** step, grad_scale)
+    _call("dwm_adamw8_multi", _p(items), _p(tab.block_item), _p(tab.block_start), tab.block_item.numel(), ADAMW_CHUNK, _p(code_m),
+          _p(code_v), *_adamw_scalars(lr, beta1, beta2, eps, weight_decay, step, grad_scale))
 
 
 # ---- gradient norm / clip coefficient / non-finite check in one read (gradnorm.hip)
-GRAD_CHUNK = 1 << 16                     # elements per workgroup of dwm_grad_sumsq_multi / dwm_grad_scale_multi
-GRAD_SUMSQ_E = GRAD_CHUNK // 1024        # squares one fp32 accumulator of grad_sumsq_multi_kernel receives per chunk, at most
-# (device, tuple of numels) -> (block_item, block_start, partials fp64, flags) on the device.  A cache of its own: _ADAMW_BLOCKS holds
-# the two lists of an optimizer, a third key there would evict one of them every step.  The scratch buffers are reused by every call
-# with this key, so calls on one list belong on one stream.
-_GRAD_TABLES: dict = {}
-
-
-def _grad_tables(dev: torch.device, numels: tuple):
-    key = (dev.index, numels)
-    tab = _GRAD_TABLES.get(key)
-    if tab is None:
-        bi, bs = [], []
-        for i, n in enumerate(numels):
-            nb = (n + GRAD_CHUNK - 1) // GRAD_CHUNK
-            bi.append(torch.full((nb,), i, dtype=torch.int32))
-            bs.append(torch.arange(nb, dtype=torch.int64) * GRAD_CHUNK)
-        while len(_GRAD_TABLES) >= 2:
-            _GRAD_TABLES.pop(next(iter(_GRAD_TABLES)))
-        bi = torch.cat(bi).to(dev)
-        tab = _GRAD_TABLES[key] = (bi, torch.cat(bs).to(dev), torch.empty(bi.numel(), dtype=torch.float64, device=dev),
-                                   torch.empty(bi.numel(), dtype=torch.int32, device=dev))
-    return tab
-
-
 def _grad_items(gs, what: str):
-    """(device, non-empty entries, their dwm_grad_item rows on the device) of a gradient list"""
+    """(non-empty entries, their dwm_grad_item rows on the device, block tables) of a gradient list"""
     gs = [g for g in gs if g.numel() > 0]
     if not gs:
-        return None, gs, None
+        return gs, None, None
     dev = gs[0].device
     for g in gs:
         if g.dtype != torch.float32 or not g.is_contiguous() or g.device != dev or not g.is_cuda or g.data_ptr() % 4:
             raise RuntimeError(f"{what}: fp32 contiguous tensors on one HIP device expected (there is no CPU fallback)")
-    items = torch.tensor([(g.data_ptr(), g.numel()) for g in gs], dtype=torch.int64).to(dev, non_blocking=True)   # dwm_grad_item[n]
-    return dev, gs, items
+    rows = [(g.data_ptr(), g.numel()) for g in gs]
+    return gs, _items(rows, dev), _block_tables(dev, GRAD_CHUNK, tuple(r[-1] for r in rows))
 
 
 def grad_sumsq_multi(gs, pre_scale: float = 1.0, max_norm: Optional[float] = None) -> torch.Tensor:
     """dwm_grad_sumsq_multi over a list of fp32 tensors (any 4-byte aligned views): device tensor [4] = (|| pre_scale * g ||_2,
     coef = pre_scale * min(1, max_norm / (norm + 1e-6)), 1.0 if any element is inf / nan else 0.0, 0).  max_norm None or <= 0: no
     clip, coef = pre_scale.  Empty tensors are dropped; an empty list gives (0, pre_scale, 0, 0) without a launch."""
-    dev, gs, items = _grad_items(gs, "grad_sumsq_multi")
+    gs, items, tab = _grad_items(gs, "grad_sumsq_multi")
     if not gs:
         return torch.tensor([0.0, pre_scale, 0.0, 0.0], dtype=torch.float32)
-    bi, bs, partials, flags = _grad_tables(dev, tuple(g.numel() for g in gs))
-    out = torch.empty(4, dtype=torch.float32, device=dev)
-    _call("dwm_grad_sumsq_multi", _p(items), _p(bi), _p(bs), bi.numel(), GRAD_CHUNK, pre_scale, 0.0 if max_norm is None else max_norm,
-          _p(partials), _p(flags), _p(out))
+    partials, flags = tab.grad_scratch()
+    out = torch.empty(4, dtype=torch.float32, device=items.device)
+    _call("dwm_grad_sumsq_multi", _p(items), _p(tab.block_item), _p(tab.block_start), tab.block_item.numel(), GRAD_CHUNK, pre_scale,
+          0.0 if max_norm is None else max_norm, _p(partials), _p(flags), _p(out))
     return out
 
 
 def grad_scale_multi_(gs, coef: float) -> None:
     """dwm_grad_scale_multi: g *= coef in place for every tensor of the list, one launch"""
-    dev, gs, items = _grad_items(gs, "grad_scale_multi_")
+    gs, items, tab = _grad_items(gs, "grad_scale_multi_")
     if not gs:
         return
-    bi, bs, _, _ = _grad_tables(dev, tuple(g.numel() for g in gs))
-    _call("dwm_grad_scale_multi", _p(items), _p(bi), _p(bs), bi.numel(), GRAD_CHUNK, coef)
+    _call("dwm_grad_scale_multi", _p(items), _p(tab.block_item), _p(tab.block_start), tab.block_item.numel(), GRAD_CHUNK, coef)
 
 
 # ------------------------------------------------------------------------------------------ composites

@@ -218,6 +218,99 @@ def test_adamw8bit_host_contract():
         bad.step()
 
 
+# ------------------------------------------------------------------------------- what step() hands to the wrappers (no kernel call)
+ROUTING_HYPER = dict(lr=0.5, beta1=0.8, beta2=0.95, eps=1e-6, weight_decay=0.125)
+
+
+def _routing_params():
+    """name -> parameter, in the optimizer's order; every gradient a fixed-seed randn"""
+    gen = torch.Generator().manual_seed(3)
+    rnd = lambda *s: torch.randn(*s, generator=gen)
+    ps = {k: torch.nn.Parameter(rnd(*s)) for k, s in (("big", (64, 128)), ("odd", (4097,)), ("small", (4095,)), ("nograd", (16,)),
+                                                      ("bf16grad", (8, 16)), ("stridedgrad", (8, 16)), ("resumed", (40,)))}
+    for k, p in ps.items():
+        if k != "nograd":
+            p.grad = rnd(*p.shape)
+    ps["bf16grad"].grad.data = ps["bf16grad"].grad.data.to(torch.bfloat16)
+    ps["stridedgrad"].grad = rnd(16, 8).t()
+    assert ps["bf16grad"].grad.dtype == torch.bfloat16 and not ps["stridedgrad"].grad.is_contiguous()
+    return ps
+
+
+def _record_wrappers(monkeypatch):
+    """T.adamw_multi_ / T.adamw8_multi_ / T.adamw_ replaced by recorders -> (multi calls as (kind, args, kwargs), adamw_ calls);
+    the adamw_ stand-in refuses what the wrapper refuses (non-contiguous tensors)"""
+    from opendwm_amd import train_ops as T
+    multi, single = [], []
+    monkeypatch.setattr(T, "adamw_multi_", lambda *a, **kw: multi.append((32, a, kw)))
+    monkeypatch.setattr(T, "adamw8_multi_", lambda *a, **kw: multi.append((8, a, kw)))
+
+    def adamw_(p, g, m, v, p_bf16, **kw):
+        single.append((p, g, m, v))
+        if not all(t.is_contiguous() for t in (p, g, m, v)):
+            raise RuntimeError("adamw_: fp32 contiguous tensors expected")
+    monkeypatch.setattr(T, "adamw_", adamw_)
+    return multi, single
+
+
+@pytest.mark.parametrize("bits", [8, 32])
+def test_step_routing(bits, monkeypatch):
+    """one step() of AdamW8bit / AdamW over a list that takes every branch of the host loop: which wrapper gets which tensors, in
+    which order, with which scalars"""
+    from opendwm_amd.train import AdamW, AdamW8bit
+    multi, single = _record_wrappers(monkeypatch)
+    ps = _routing_params()
+    kw = dict(lr=ROUTING_HYPER["lr"], betas=(ROUTING_HYPER["beta1"], ROUTING_HYPER["beta2"]), eps=ROUTING_HYPER["eps"],
+              weight_decay=ROUTING_HYPER["weight_decay"])
+    opt = AdamW8bit(ps.values(), min_8bit_size=4096, **kw) if bits == 8 else AdamW(ps.values(), **kw)
+    resumed = ps["resumed"]
+    opt.load_state_dict({"state": {6: {"step": torch.tensor(5.0), "exp_avg": torch.full((40,), 0.5), "exp_avg_sq": torch.ones(40)}},
+                         "param_groups": opt.state_dict()["param_groups"]})
+    assert list(opt.state) == [resumed]
+    grads = {k: (None if p.grad is None else p.grad.clone()) for k, p in ps.items()}
+    assert opt.step(grad_scale=0.25) is None
+
+    eight = ["big", "odd"] if bits == 8 else []
+    fresh32 = [k for k in ps if k not in eight + ["nograd", "resumed"]]
+    want = ([(8, 1, eight)] if eight else []) + [(32, 1, fresh32), (32, 6, ["resumed"])]
+    assert [(kind, c["step"]) for kind, _, c in multi] == [(kind, step) for kind, step, _ in want]        # one call per (kind, step)
+    for (kind, args, call), (_, step, names) in zip(multi, want):
+        assert call == dict(ROUTING_HYPER, step=step, grad_scale=0.25)
+        assert len(args) == (7 if kind == 8 else 5) and all(len(a) == len(names) for a in args)
+        states = [opt.state[ps[k]] for k in names]
+        keys = ("exp_avg", "exp_avg_absmax", "exp_avg_sq", "exp_avg_sq_absmax") if kind == 8 else ("exp_avg", "exp_avg_sq")
+        assert all(a.data_ptr() == ps[k].data_ptr() and a.shape == ps[k].shape for a, k in zip(args[0], names))
+        for lst, key in zip(args[2:-1], keys):
+            assert all(a is st[key] for a, st in zip(lst, states)), key                                  # moments by identity
+        assert all(st["exp_avg"].dtype == (torch.uint8 if kind == 8 else torch.float32) for st in states)
+        for g, k in zip(args[1], names):
+            assert g.dtype == torch.float32 and g.is_contiguous() and torch.equal(g, grads[k].float())
+            assert torch.equal(ps[k].grad, grads[k])                                                      # the gradient itself is left alone
+            if k not in ("bf16grad", "stridedgrad"):
+                assert g is ps[k].grad                                                                    # no copy where none is needed
+        assert all(sh is None for sh in args[-1])                                                         # CPU tensors carry no shadow
+    for k, p in ps.items():
+        if k == "nograd":
+            assert p not in opt.state                               # no state, no step
+        else:
+            assert float(opt.state[p]["step"]) == (6.0 if k == "resumed" else 1.0)
+    assert opt.t == 6 and single == []                              # T.adamw_ is not part of step()
+
+    # a transposed parameter: RuntimeError from step(), raised inside the loop over the group - the parameters before it have
+    # counted the step, no launch was made for the group
+    multi.clear()
+    first = torch.nn.Parameter(torch.zeros(64, 128))
+    transposed = torch.nn.Parameter(torch.zeros(128, 128).t())
+    last = torch.nn.Parameter(torch.zeros(8))
+    for p in (first, transposed, last):
+        p.grad = torch.ones_like(p)
+    opt = (AdamW8bit if bits == 8 else AdamW)([first, transposed, last])
+    with pytest.raises(RuntimeError):
+        opt.step()
+    assert multi == [] and single == []
+    assert float(opt.state[first]["step"]) == 1.0 and last not in opt.state
+
+
 def test_abi_item_mirror_matches_header():
     """the row train_ops.adamw8_multi_ writes per tensor is dwm_adamw8_item: eight 8-byte fields in the header's order"""
     import ctypes

@@ -183,10 +183,13 @@ def test_trainer_grad_conditioning_argument():
 
 def test_block_tables_cover_every_element_once():
     """the table builder (host code; the kernels index with it): ceil(n / chunk) consecutive-start blocks per tensor, in order, and a
-    cache entry of its own per (device, numels)"""
+    cache entry per (device, chunk, numels) that the gradient list and the two lists of an optimizer can hold side by side"""
     from opendwm_amd import train_ops as T
+    cpu = torch.device("cpu")
+    T._BLOCK_TABLES.clear()
     numels = (1, 3, T.GRAD_CHUNK - 1, T.GRAD_CHUNK, T.GRAD_CHUNK + 1, 3 * T.GRAD_CHUNK + 5)
-    bi, bs, partials, flags = T._grad_tables(torch.device("cpu"), numels)
+    tab = T._block_tables(cpu, T.GRAD_CHUNK, numels)
+    bi, bs, (partials, flags) = tab.block_item, tab.block_start, tab.grad_scratch()
     assert bi.dtype == torch.int32 and bs.dtype == torch.int64 and partials.dtype == torch.float64 and flags.dtype == torch.int32
     assert bi.numel() == bs.numel() == partials.numel() == flags.numel() == sum(-(-n // T.GRAD_CHUNK) for n in numels)
     covered = [0] * len(numels)
@@ -194,5 +197,14 @@ def test_block_tables_cover_every_element_once():
         assert s == covered[i] and s < numels[i]                  # consecutive starts, never an empty block
         covered[i] = min(s + T.GRAD_CHUNK, numels[i])
     assert tuple(covered) == numels and bi.tolist() == sorted(bi.tolist())
-    assert T._grad_tables(torch.device("cpu"), numels)[0] is bi and not any(k in T._ADAMW_BLOCKS for k in T._GRAD_TABLES)
-    T._GRAD_TABLES.clear()
+    assert T._block_tables(cpu, T.GRAD_CHUNK, numels).block_item is bi and tab.grad_scratch()[0] is partials
+    # the gradient list and the fp32 / 8-bit lists of an optimizer, asked for in rotation as a training loop does: nothing is evicted
+    keys = [(T.GRAD_CHUNK, numels), (T.ADAMW_CHUNK, numels[:3]), (T.ADAMW_CHUNK, numels[3:])]
+    first = [T._block_tables(cpu, *k) for k in keys]
+    assert first[0] is tab
+    for _ in range(3):
+        T._block_tables(cpu, T.GRAD_CHUNK, (7,))                  # the spare entry: an occasional fourth list evicts none of them
+        for k, t0 in zip(keys, first):
+            t = T._block_tables(cpu, *k)
+            assert t is t0 and t.block_item is t0.block_item and t.block_start is t0.block_start
+    T._BLOCK_TABLES.clear()

@@ -323,3 +323,57 @@ def test_trainer_8bit_optimizer_in_fused_mode(problem):
     losses = [_step(pb, tr) for _ in range(6)]
     _log("grad_conditioning_8bit", losses=losses, skipped=tr.skipped_steps)
     assert all(l == l and abs(l) != float("inf") for l in losses) and losses[-1] < losses[0] and tr.optimizer.t == 6
+
+
+# ------------------------------------------------------------------------------- one table cache for the three tensor-list kernels
+def _interleaved_run(dev, clear_cache):
+    """four rounds of grad_sumsq_multi -> adamw8_multi_ -> adamw_multi_ on an fp32-moment list, an 8-bit list and the gradient list of
+    both, grad_scale taken from the norm call -> (every parameter, moment, code, scale and norm output on the host, the table
+    pointers in the cache after each round).  clear_cache: the table cache is emptied before every call."""
+    from opendwm_amd import quant8
+    from opendwm_amd import train_ops as T
+    numels = [5, 256, 4099, T.ADAMW_CHUNK + 1]
+    gen = torch.Generator().manual_seed(11)
+    rnd = lambda: [torch.randn(n, generator=gen).to(dev) for n in numels]
+    zeros = lambda dtype=f32, fill=0: [torch.full((n,), fill, dtype=dtype, device=dev) for n in numels]
+    scales = lambda: [torch.zeros(quant8.n_blocks(n), device=dev) for n in numels]
+    p32, m32, v32, p8 = rnd(), zeros(), zeros(), rnd()
+    mq, ma, vq, va = zeros(torch.uint8, quant8.zero_code(True)), scales(), zeros(torch.uint8, quant8.zero_code(False)), scales()
+    hyper = dict(lr=1e-3, beta1=0.9, beta2=0.975, eps=1e-8, weight_decay=0.01)
+    none = [None] * len(numels)
+
+    def call(fn, *a, **kw):
+        if clear_cache:
+            T._BLOCK_TABLES.clear()
+        return fn(*a, **kw)
+
+    T._BLOCK_TABLES.clear()
+    norms, ptrs = [], []
+    for step in range(1, 5):
+        g32, g8 = rnd(), rnd()
+        out = call(T.grad_sumsq_multi, g32 + g8, 0.5, 1.0)
+        norms.append(out.cpu())
+        coef = norms[-1][1].item()
+        assert 0.0 < coef < 0.5 and norms[-1][2].item() == 0.0                # the clip is active, nothing is non-finite
+        call(T.adamw8_multi_, p8, g8, mq, ma, vq, va, none, step=step, grad_scale=coef, **hyper)
+        call(T.adamw_multi_, p32, g32, m32, v32, none, step=step, grad_scale=coef, **hyper)
+        ptrs.append({k: (t.block_item.data_ptr(), t.block_start.data_ptr()) for k, t in T._BLOCK_TABLES.items()})
+    torch.cuda.synchronize()
+    keys = {(dev.index, T.GRAD_CHUNK, tuple(numels + numels)), (dev.index, T.ADAMW_CHUNK, tuple(numels))}
+    return [t.cpu() for lst in (p32, m32, v32, p8, mq, ma, vq, va) for t in lst] + norms, ptrs, keys
+
+
+def test_shared_tables_interleaved(dev):
+    """the gradient list and the two optimizer lists (equal numels: ONE entry serves the fp32 and the 8-bit launch) live side by
+    side in the cache: the kernels get the same table buffers in every round, and every result is bit for bit what freshly built
+    tables give"""
+    from opendwm_amd import train_ops as T
+    cached, ptrs, keys = _interleaved_run(dev, clear_cache=False)
+    assert set(ptrs[0]) == keys and all(p == ptrs[0] for p in ptrs), ptrs
+    fresh, one_entry, _ = _interleaved_run(dev, clear_cache=True)
+    assert all(len(p) == 1 for p in one_entry)                                 # the cache really was empty before each call
+    assert len(cached) == len(fresh) == 8 * 4 + 4
+    for i, (a, b) in enumerate(zip(cached, fresh)):
+        assert a.dtype == b.dtype and torch.equal(a.view(torch.uint8), b.view(torch.uint8)), i
+    assert all(bool(cached[i].any()) for i in (4, 8, 20, 23))                  # fp32 moments and 8-bit scales have left zero
+    T._BLOCK_TABLES.clear()
