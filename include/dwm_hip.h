@@ -628,6 +628,17 @@ typedef struct dwm_block_permute_args {
 } dwm_block_permute_args;
 int dwm_block_permute(const dwm_block_permute_args* args, void* stream);
 
+/* Head exchange: a pure copy of rows x S x R x Dr elements of `elem_size` (2 or 4) bytes between
+ *   the row-major layout  [row][s][j][Dr]  with a row stride of `ld` elements (ld >= S * R * Dr: e.g. a fused q | k | v projection,
+ *   S = 3 stacked tensors of R head groups of Dr = (heads / R) * 64 channels each, or a column slice of a wider buffer), and
+ *   the dense layout      [j][row][s][Dr]  (chunk j = what goes to / came from rank j of an all-to-all).
+ * dir = 0 (split): src row-major -> dst dense.  dir = 1 (merge): src dense -> dst row-major.
+ * Dr * elem_size and ld * elem_size must be multiples of 16 and both pointers 16-byte aligned (DWM_EALIGN); fewer than 2^31
+ * 16-byte pieces in all (DWM_EUNSUPPORTED).  The pack / unpack of the frame shard's "heads" plan (opendwm_amd/sharding.py: "my
+ * frames, all heads" <-> "all frames, my heads" around the temporal attention; no reference counterpart). */
+int dwm_head_exchange(const void* src, void* dst, int64_t rows, int32_t S, int32_t R, int64_t Dr, int32_t elem_size, int64_t ld,
+                      int32_t dir, void* stream);
+
 /* y fp32 [rows, ldy] (+)= x bf16 [rows, ldx] */
 int dwm_cast_bf16_to_f32(const void* x, int64_t ldx, float* y, int64_t ldy, int64_t rows, int64_t cols,
                          int32_t accumulate, void* stream);

@@ -202,6 +202,7 @@ SIGNATURES = {
     "dwm_grad_sumsq_multi": (_i32, [_vp, _vp, _vp, _i64, _i64, _f32, _f32, _vp, _vp, _vp, _vp]),
     "dwm_grad_scale_multi": (_i32, [_vp, _vp, _vp, _i64, _i64, _f32, _vp]),
     "dwm_block_permute": (_i32, [C.POINTER(BlockPermuteArgs), _vp]),
+    "dwm_head_exchange": (_i32, [_vp, _vp, _i64, _i32, _i32, _i64, _i32, _i64, _i32, _vp]),
     "dwm_cast_bf16_to_f32": (_i32, [_vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp]),
     "dwm_groupnorm_bwd": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _f32, _vp, _vp, _i32, _i32, _vp, _vp, _vp,
                                  C.POINTER(RowMap2D), C.POINTER(GnImgMap), _vp]),

@@ -441,11 +441,13 @@ class VTSelfAttentionBlock(nn.Module):
             rows_per_emb: int = 1, group_mask: Optional[torch.Tensor] = None,
             dense_mask: Optional[torch.Tensor] = None,
             blend_alpha: Optional[torch.Tensor] = None, rows_per_alpha: int = 1,
-            blend_into: Optional[torch.Tensor] = None) -> torch.Tensor:
+            blend_into: Optional[torch.Tensor] = None, head_exchange=None) -> torch.Tensor:
         """h [rows, D] bf16 (or the fp32 residual stream of a bf16 forward, `stream32`: the block's own stream x is then fp32
         as well).  x = h + emb[row // rows_per_emb]; y = block(x); if blend_alpha is
         given the result alpha*blend_into + (1-alpha)*y is written into blend_into (the mixer of
-        crossview_temporal_dit.py:320-327 / :363-370)."""
+        crossview_temporal_dit.py:320-327 / :363-370).
+        head_exchange: a sharding.FrameShard of R ranks - h holds the rows of this rank's frames only, and the attention alone runs
+        on all frames of heads / R heads: `rowmap` addresses the received layout (ops.rowmap_temporal_*_exchanged)."""
         D = self.dim
         pk = self.packed()
         x32 = stream32(h)
@@ -463,8 +465,21 @@ class VTSelfAttentionBlock(nn.Module):
         y = ln(xs, self.norm1, out=y)
         qkv = self.attn1.project_qkv(y)
         ao = y     # norm1 output is dead once qkv exists
-        ops.attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], ao, rowmap, self.heads,
-                      group_mask=group_mask, dense_mask=dense_mask, variant=self.attn1.attn_variant | ATTN_VARIANT)
+        if head_exchange is None:
+            ops.attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], ao, rowmap, self.heads,
+                          group_mask=group_mask, dense_mask=dense_mask, variant=self.attn1.attn_variant | ATTN_VARIANT)
+        else:
+            # "my frames, all heads" -> "all frames, my heads" and back (sharding.py).  The q / k RMSNorm of the projection's epilogue
+            # and a pre-scaled q are per head, so they travel with the heads.
+            fs, rows = head_exchange, qkv.shape[0]
+            if group_mask is not None or dense_mask is not None or self.heads % fs.size:
+                raise RuntimeError("VTSelfAttentionBlock.run: the head exchange takes no mask and needs heads % ranks == 0")
+            Dr = D // fs.size
+            rx = fs.heads_gather(qkv, rows, 3)                                            # [R * rows, q | k | v of my heads]
+            ox = torch.empty(fs.size * rows, Dr, dtype=rx.dtype, device=rx.device)
+            ops.attention(rx[:, :Dr], rx[:, Dr:2 * Dr], rx[:, 2 * Dr:], ox, rowmap, self.heads // fs.size,
+                          variant=self.attn1.attn_variant | ATTN_VARIANT)
+            fs.heads_scatter(ox, rows, out=ao)
         to_out = self.attn1.to_out[0]
         _resid_into(xs, ao, _bf(to_out.weight), _bf(to_out.bias))
 

@@ -606,3 +606,77 @@ extern "C" int dwm_block_permute(const dwm_block_permute_args* a, void* stream) 
     hipLaunchKernelGGL(block_permute_kernel, dim3((unsigned)(nb * chunks)), dim3(256), 0, (hipStream_t)stream, p);
     return dwm_launch_status();
 }
+
+
+// ---- head exchange (frame-shard "heads" plan, see dwm_hip.h): rows x S x R x Dr elements between the row-major layout of a fused
+// projection ([row][s][j][Dr], row stride ld) and the dense per-destination layout of the all-to-all ([j][row][s][Dr]).  A run of
+// Dr elements is >= 128 bytes, far too small for a workgroup of its own (block_permute_kernel's unit): the copy is indexed by the
+// 16-byte chunk of the DENSE side instead, so a wave moves 1 KiB that is contiguous there and a sequence of whole runs on the
+// strided side, and a capped grid strides over the chunks.
+namespace {
+struct HeadExP {
+    const char* src; char* dst;
+    int64_t ld_bytes, run_bytes;                  // row stride of the strided side; one run = Dr elements
+    uint32_t total, R;                            // 16-byte chunks in all
+    FastDiv dc, ds, drows;                        // divisors: chunks per run, S, rows
+};
+// strided-side byte offset of dense chunk g; dense order: (j, row, s, chunk)
+DWM_DEVINL int64_t head_ex_offset(const HeadExP& p, uint32_t g) {
+    const uint32_t t = fdiv(g, p.dc), c = g - t * p.dc.d;
+    const uint32_t t2 = fdiv(t, p.ds), s = t - t2 * p.ds.d;
+    const uint32_t j = fdiv(t2, p.drows), row = t2 - j * p.drows.d;
+    return (int64_t)row * p.ld_bytes + (int64_t)(s * p.R + j) * p.run_bytes + (int64_t)c * 16;
+}
+template <int MERGE>
+__global__ void __launch_bounds__(256)
+head_exchange_kernel(const HeadExP p) {
+    const char* __restrict__ src = p.src;
+    char* __restrict__ dst = p.dst;
+    const uint32_t step = gridDim.x * 1024u;
+    for (uint32_t b0 = blockIdx.x * 1024u; b0 < p.total; b0 += step) {                  // p.total < 2^31: b0 cannot wrap
+        const uint32_t g0 = b0 + threadIdx.x;
+        if (b0 + 1024u <= p.total) {                                                      // a whole pass: four loads in flight per lane
+            const int64_t o0 = head_ex_offset(p, g0), o1 = head_ex_offset(p, g0 + 256u), o2 = head_ex_offset(p, g0 + 512u),
+                          o3 = head_ex_offset(p, g0 + 768u);
+            const int64_t d0 = (int64_t)g0 * 16;
+            const uint4 v0 = *(const uint4*)(src + (MERGE ? d0 : o0));
+            const uint4 v1 = *(const uint4*)(src + (MERGE ? d0 + 4096 : o1));
+            const uint4 v2 = *(const uint4*)(src + (MERGE ? d0 + 8192 : o2));
+            const uint4 v3 = *(const uint4*)(src + (MERGE ? d0 + 12288 : o3));
+            *(uint4*)(dst + (MERGE ? o0 : d0)) = v0;
+            *(uint4*)(dst + (MERGE ? o1 : d0 + 4096)) = v1;
+            *(uint4*)(dst + (MERGE ? o2 : d0 + 8192)) = v2;
+            *(uint4*)(dst + (MERGE ? o3 : d0 + 12288)) = v3;
+        } else {                                                                          // the last, partial pass
+            for (uint32_t g = g0; g < p.total; g += 256u) {
+                const int64_t o = head_ex_offset(p, g), d = (int64_t)g * 16;
+                *(uint4*)(dst + (MERGE ? o : d)) = *(const uint4*)(src + (MERGE ? d : o));
+            }
+        }
+    }
+}
+}  // namespace
+
+extern "C" int dwm_head_exchange(const void* src, void* dst, int64_t rows, int32_t S, int32_t R, int64_t Dr, int32_t elem_size,
+                                 int64_t ld, int32_t dir, void* stream) {
+    if (src == nullptr || dst == nullptr || rows <= 0 || S <= 0 || R <= 0 || Dr <= 0) return DWM_EINVAL;
+    if ((elem_size != 2 && elem_size != 4) || (dir != 0 && dir != 1)) return DWM_EINVAL;
+    if (S > (1 << 16) || R > (1 << 16) || Dr > (1ll << 30) || ld > (1ll << 40)) return DWM_EUNSUPPORTED;
+    if (ld < (int64_t)S * R * Dr) return DWM_EINVAL;
+    const int64_t run = Dr * elem_size, ldb = ld * elem_size;
+    if (run % 16 != 0 || ldb % 16 != 0 || !dwm_aligned16(src) || !dwm_aligned16(dst)) return DWM_EALIGN;
+    if (rows >= (1ll << 31)) return DWM_EUNSUPPORTED;
+    const int64_t per_row = (int64_t)S * R * (run / 16);               // < 2^62
+    if (per_row >= (1ll << 31) || rows * per_row >= (1ll << 31)) return DWM_EUNSUPPORTED;
+    const int64_t total = rows * per_row;
+    HeadExP p;
+    p.src = (const char*)src; p.dst = (char*)dst; p.ld_bytes = ldb; p.run_bytes = run;
+    p.total = (uint32_t)total; p.R = (uint32_t)R;
+    p.dc = make_fastdiv((uint32_t)(run / 16)); p.ds = make_fastdiv((uint32_t)S); p.drows = make_fastdiv((uint32_t)rows);
+    // 16 KiB per workgroup and pass; at most 4096 workgroups (16 per CU), which stride over the rest
+    int64_t grid = (total + 1023) / 1024;
+    if (grid > 4096) grid = 4096;
+    if (dir == 0) hipLaunchKernelGGL(head_exchange_kernel<0>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(head_exchange_kernel<1>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p);
+    return dwm_launch_status();
+}

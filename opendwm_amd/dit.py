@@ -438,8 +438,11 @@ class DiTCrossviewTemporalConditionModel(_Base):
         # frames of the sample; T is the local frame count, Tg the sample's
         fs, cam_all = self.frame_shard, None
         Tg = T if fs is None else T * fs.size
+        # t_plan: what the temporal blocks exchange - "rows": they run on all frames of this rank's token rows; "heads": on h itself
+        # (local frames, all token rows), only their attention runs on all frames of this rank's heads
+        t_plan = None
         if fs is not None and self.enable_temporal:
-            fs.check(height, self.temporal_attention_type)
+            t_plan = fs.plan(height, self.num_attention_heads, self.temporal_attention_type)
 
         # compute dtype: bf16 (storage bf16, fp32 accumulation / statistics), or - `model.compute_dtype = torch.float32` -
         # the fp32 accuracy path (north_star's 1e-3 tolerance; the reference runs this graph in fp32 when no autocast /
@@ -482,7 +485,7 @@ class DiTCrossviewTemporalConditionModel(_Base):
             if camera_intrinsics_norm is None or camera2referego is None:
                 raise RuntimeError("perspective_modeling_type='explicit' needs camera_intrinsics_norm and camera2referego")
             ray_feat = self.rayencoder.features(camera_intrinsics_norm, camera2referego, height, width)
-            if fs is not None and self.enable_temporal and self.enable_crossview and not self.disable_view_emb_on_temporal_module:
+            if t_plan == "rows" and self.enable_crossview and not self.disable_view_emb_on_temporal_module:
                 # the temporal blocks run on "all frames, my token rows" (sharding.py): the features of those rows for every
                 # frame of the sample, from the gathered per-image camera matrices (a few hundred bytes per image) - the
                 # features themselves never cross the links
@@ -533,6 +536,9 @@ class DiTCrossviewTemporalConditionModel(_Base):
         seq_sin = view_sin = None
         if self.enable_temporal and self.temporal_block_layers:
             seq_sin = self._index_sinusoid("t", B, Tg, V, D, h.device, cd)
+            if t_plan == "heads":                                                       # this rank's frames of the sample
+                t0, t1 = fs.frame_range(Tg)
+                seq_sin = seq_sin.view(B, Tg, V, -1)[:, t0:t1].reshape(B * T * V, -1)
             t_alpha = self._mixer_alphas(self.time_mixers, disable_temporal, B)
         if self.enable_crossview and self.crossview_block_layers:
             view_sin = self._index_sinusoid("v", B, T, V, D, h.device, cd)
@@ -558,13 +564,14 @@ class DiTCrossviewTemporalConditionModel(_Base):
                 seq = seq_sin
                 use_cam = self.enable_crossview and not self.disable_view_emb_on_temporal_module \
                     and view_cam_emb is not None
-                if use_cam and fs is not None and cam_all is None:
+                by_rows = t_plan == "rows"
+                if use_cam and by_rows and cam_all is None:
                     cam_all = fs.gather_frames(view_cam_emb.view(B, T, V, D), 1).view(-1, D)
-                seq_emb = self.time_pos_embeds[k].run(seq, res=(view_cam_emb if fs is None else cam_all) if use_cam else None)
+                seq_emb = self.time_pos_embeds[k].run(seq, res=(cam_all if by_rows else view_cam_emb) if use_cam else None)
                 rpe = N
                 if ray_feat is not None and self.enable_crossview and not self.disable_view_emb_on_temporal_module:
-                    seq_emb = ops.gemm(ray_feat if fs is None else ray_rows, self.rayencoder.packed(), None, epilogue=ops.EPI_RESID,
-                                       res=seq_emb, res_mod=-(N if fs is None else (height // fs.size) * width))
+                    seq_emb = ops.gemm(ray_rows if by_rows else ray_feat, self.rayencoder.packed(), None, epilogue=ops.EPI_RESID,
+                                       res=seq_emb, res_mod=-((height // fs.size) * width if by_rows else N))
                     rpe = 1
                 tt = self.temporal_attention_type
                 mk = ops.rowmap_temporal_full if tt == "full" else \
@@ -574,6 +581,12 @@ class DiTCrossviewTemporalConditionModel(_Base):
                     self.temporal_transformer_blocks[k].run(
                         h, mk(B, T, V, height, width), emb=seq_emb, rows_per_emb=rpe,
                         blend_alpha=alpha, rows_per_alpha=T * V * N, blend_into=h)
+                elif t_plan == "heads":
+                    # the block stays on my frames; its attention exchanges heads for frames (blocks.VTSelfAttentionBlock.run)
+                    mkx = ops.rowmap_temporal_full_exchanged if tt == "full" else ops.rowmap_temporal_rowwise_exchanged
+                    self.temporal_transformer_blocks[k].run(
+                        h, mkx(B, T, fs.size, V, height, width), emb=seq_emb, rows_per_emb=rpe,
+                        blend_alpha=alpha, rows_per_alpha=T * V * N, blend_into=h, head_exchange=fs)
                 else:
                     # frames of this sample live on other ranks: all frames of MY token rows, block + mixer, and back
                     hl = height // fs.size

@@ -345,7 +345,26 @@ def block_permute(src: torch.Tensor, dst: torch.Tensor, dims, src_strides, block
     return dst
 
 
-ATTN_Q_PRESCALED = 1 << 15      # dwm_attn_args.variant: q arrives with scale * log2(e) folded in by its producer
+def head_exchange(src: torch.Tensor, dst: torch.Tensor, rows: int, S: int, R: int, Dr: int, merge: bool = False) -> torch.Tensor:
+    """split (merge=False): src [rows, S * R * Dr] with contiguous rows (a column slice of a wider buffer is fine) -> dst dense
+    [R, rows, S, Dr]; merge: src dense [R, rows, S, Dr] -> dst [rows, S * R * Dr].  dwm_head_exchange: the pack / unpack of the frame
+    shard's head exchange (sharding.py), bf16 or fp32."""
+    wide, dense = (dst, src) if merge else (src, dst)
+    if not (src.is_cuda and dst.is_cuda and src.dtype == dst.dtype and src.element_size() in (2, 4)):
+        raise RuntimeError("head_exchange: device tensors of one 2- or 4-byte dtype expected")
+    if min(rows, S, R, Dr) <= 0:
+        raise RuntimeError("head_exchange: rows, S, R and Dr must be positive")
+    if wide.dim() != 2 or wide.stride(1) != 1 or tuple(wide.shape) != (rows, S * R * Dr) or (rows > 1 and wide.stride(0) < S * R * Dr):
+        raise RuntimeError(f"head_exchange: the row-major side must be [rows, S * R * Dr] = [{rows}, {S * R * Dr}] with contiguous rows, "
+                           f"got {tuple(wide.shape)} strides {wide.stride()}")
+    if not dense.is_contiguous() or dense.numel() != rows * S * R * Dr:
+        raise RuntimeError("head_exchange: the dense side must be contiguous with rows * S * R * Dr elements")
+    ld = wide.stride(0) if rows > 1 else max(wide.stride(0), S * R * Dr)
+    _call("dwm_head_exchange", src.data_ptr(), dst.data_ptr(), rows, S, R, Dr, src.element_size(), ld, 1 if merge else 0)
+    return dst
+
+
+ATTN_Q_PRESCALED = 1 << 15     # dwm_attn_args.variant: q arrives with scale * log2(e) folded in by its producer
 ATTN_STREAM = 1 << 12           # ... the one-wave-per-SIMD streaming form of the resident kernel (attention_stream.hip): the library's default where it covers the launch
 ATTN_RES12 = 1 << 13            # ... keep the 12-wave resident kernel there (A/B measurements)
 
@@ -560,6 +579,26 @@ def rowmap_temporal_full(B: int, T: int, V: int, h: int, w: int) -> RowMap:
     return RowMap(L0=T * h * w, n_problems=B * V,
                   pdiv=(V, 1, 1), pmod=(BIG, V, 1), pstride=(T * V * h * w, h * w, 0),
                   ldiv=(h * w, BIG), lstride=(1, V * h * w, 0))
+
+
+# The temporal maps over the RECEIVED layout of the frame shard's head exchange (sharding.FrameShard.heads_gather): rows ordered
+# (i, b, tl, v, n) with i the source rank, Tl = T / R frames per rank, frame t = i * Tl + tl, n = token of the h x w grid.  Problems and
+# tokens are enumerated exactly as by the unsharded maps above, so the attention reads q / k / v from the receive buffer as it
+# arrived and writes the send buffer of the way back: no rearranged copy on either side.
+def rowmap_temporal_full_exchanged(B: int, Tl: int, R: int, V: int, h: int, w: int) -> RowMap:
+    """rowmap_temporal_full(B, R * Tl, V, h, w) on rows ordered (i, b, tl, v, n)."""
+    N = h * w
+    return RowMap(L0=R * Tl * N, n_problems=B * V,
+                  pdiv=(V, 1, 1), pmod=(BIG, V, 1), pstride=(Tl * V * N, N, 0),
+                  ldiv=(N, Tl), lstride=(1, V * N, B * Tl * V * N))
+
+
+def rowmap_temporal_rowwise_exchanged(B: int, Tl: int, R: int, V: int, h: int, w: int) -> RowMap:
+    """rowmap_temporal_rowwise(B, R * Tl, V, h, w) on rows ordered (i, b, tl, v, n)."""
+    N = h * w
+    return RowMap(L0=R * Tl * w, n_problems=B * V * h,
+                  pdiv=(V * h, h, 1), pmod=(BIG, V, h), pstride=(Tl * V * N, N, w),
+                  ldiv=(w, Tl), lstride=(1, V * N, B * Tl * V * N))
 
 
 def rowmap_temporal_pointwise(B: int, T: int, V: int, h: int, w: int) -> RowMap:

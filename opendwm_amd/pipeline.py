@@ -51,10 +51,13 @@ class CTSDDenoiser:
         scheduler step, frames outside the schedule range left untouched (:1498-1507, :1554-1572)."""
 
     def __init__(self, model, guidance_scale: float = 4.0, inference_steps: int = 40, shift: float = 3.0,
-                 cfg_group=None, frame_group=None):
+                 cfg_group=None, frame_group=None, frame_exchange: str = "rows"):
         """frame_group: a torch.distributed process group whose R ranks hold T/R frames each of ONE sample
         (opendwm_amd.sharding: one all-to-all before and after every temporal block; everything else is local).  Every
         rank passes the same full latents / conditions to prepare() and gets the full result() back.
+        frame_exchange: what the temporal blocks of the frame shards exchange (sharding.FrameShard): "rows" = token rows (rowwise /
+        pointwise temporal attention, token rows % R == 0), "heads" = attention heads around the attention alone (full / rowwise
+        temporal attention, heads % R == 0), "auto" = rows where they serve, else heads.
 
         cfg_group: a torch.distributed process group of size 2 -> classifier-free-guidance split: the
         two halves of the CFG batch are independent inside the model, so rank 0 of the group runs the unconditional
@@ -67,7 +70,9 @@ class CTSDDenoiser:
         self.frame_shard = None
         if frame_group is not None:
             from .sharding import FrameShard
-            self.frame_shard = FrameShard(frame_group)
+            self.frame_shard = FrameShard(frame_group, temporal_exchange=frame_exchange)
+        elif frame_exchange != "rows":
+            raise ValueError("frame_exchange chooses the exchange of a frame_group: pass one")
         if cfg_group is not None:
             import torch.distributed as dist
             if dist.get_world_size(cfg_group) != 2:
