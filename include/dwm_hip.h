@@ -457,6 +457,15 @@ int dwm_cfg_ddim_step(const void* pred, int32_t pred_is_f32, int32_t cfg, float*
                       const float* noise, const float* coef, int64_t n, int64_t group_elems, float guidance,
                       int32_t prediction_type, float clip_range, int32_t use_clipped_model_output, void* stream);
 
+/* dwm_cfg_ddim_step with one int32 flag per group (skip, may be NULL = dwm_cfg_ddim_step): a group with skip[g] != 0 keeps its
+ * latents, x0_out and model_in entries bit-unchanged.  Diffusion forcing: the frames outside the schedule range, the
+ * `torch.where(in_schedule_range, staging_latents, latents)` of ctsd.py:1565-1572; full-sequence mode: the reference frames,
+ * whose clean latents stay in model_in (ctsd.py:1514-1519). */
+int dwm_cfg_ddim_step_masked(const void* pred, int32_t pred_is_f32, int32_t cfg, float* latents, void* model_in, float* x0_out,
+                             const float* noise, const float* coef, int64_t n, int64_t group_elems, float guidance,
+                             int32_t prediction_type, float clip_range, int32_t use_clipped_model_output, const int32_t* skip,
+                             void* stream);
+
 /* classifier-free guidance + one step of a linear multistep scheduler on fp32 latents (SD 2.1 configs:
  * diffusers DPMSolverMultistepScheduler, dpmsolver++ / midpoint, called at ctsd.py:1548-1575):
  *   out = u + g (c - u);  x0 = kx * x + ko * out  (epsilon: kx = 1/alpha_t, ko = -sigma_t/alpha_t; v: kx = alpha_t, ko = -sigma_t)
@@ -464,6 +473,19 @@ int dwm_cfg_ddim_step(const void* pred, int32_t pred_is_f32, int32_t cfg, float*
  * The scalar coefficients are the scheduler's per-step constants, computed on the host. */
 int dwm_cfg_multistep(const void* pred, float* latents, float* x0_prev, void* model_in, int64_t n, float guidance,
                       float kx, float ko, float A, float B, float C, void* stream);
+
+/* dwm_cfg_multistep with the coefficients in device memory, so that a step captured into a HIP graph replays with the numbers
+ * of the step it is replayed for: coef fp32 [coef_rows, 5] = (kx, ko, A, B, C) per group of `group_elems` consecutive elements
+ * (one (sample, frame, view) image; group_elems % 4 == 0, n % group_elems == 0), coef_rows = n / group_elems, or 1 = one row for
+ * every group.  keep_model_in (int32 [n / group_elems], may be NULL): a group with a flag != 0 is a reference frame - neither
+ * half of model_in is written there, so the clean latents the caller stored stay in the model input (ctsd.py:1514-1526); its
+ * latents / x0_prev entries are still updated and are never read (the result takes those frames from image_latents,
+ * ctsd.py:1623-1627).  pred / model_in: bf16 [2, n]; the _f32 form takes both in fp32 (the accuracy path). */
+int dwm_cfg_multistep_grouped(const void* pred, float* latents, float* x0_prev, void* model_in, int64_t n, float guidance,
+                              const float* coef, int64_t coef_rows, const int32_t* keep_model_in, int64_t group_elems, void* stream);
+int dwm_cfg_multistep_grouped_f32(const float* pred, float* latents, float* x0_prev, float* model_in, int64_t n, float guidance,
+                                  const float* coef, int64_t coef_rows, const int32_t* keep_model_in, int64_t group_elems,
+                                  void* stream);
 
 /* dst bf16 <- src fp32 (n % 4 == 0) */
 int dwm_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream);

@@ -163,6 +163,9 @@ SIGNATURES = {
     "dwm_frame_affine": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
     "dwm_cfg_ddim_step": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _i32, _f32, _i32, _vp]),
     "dwm_cfg_multistep": (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _vp]),
+    "dwm_cfg_ddim_step_masked": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _i32, _f32, _i32, _vp, _vp]),
+    "dwm_cfg_multistep_grouped": (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _vp, _i64, _vp, _i64, _vp]),
+    "dwm_cfg_multistep_grouped_f32": (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _vp, _i64, _vp, _i64, _vp]),
     "dwm_unshuffle_tokens": (_i32, [_vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     "dwm_avgpool2_tokens": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "dwm_add_inplace": (_i32, [_vp, _vp, _i64, _vp]),

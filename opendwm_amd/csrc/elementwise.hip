@@ -128,6 +128,51 @@ cfg_multistep_kernel(const T* __restrict__ pred, float* __restrict__ lat, float*
     }
 }
 
+// the same update with the coefficients in device memory (a step captured into a HIP graph cannot take them as launch scalars):
+//   coef[g * coef_stride + 0..4] = (kx, ko, A, B, C) of the group g = element / group_elems (one (sample, frame, view) image);
+//   coef_stride = 0 broadcasts one row.  keep[g] != 0 marks a reference group: neither half of model_in is written there, so
+//   the clean latents the caller put in stay (ctsd.py:1514-1519); its latents / x0_prev entries are updated and never read.
+template <typename T>
+__global__ void __launch_bounds__(256)
+cfg_multistep_grouped_kernel(const T* __restrict__ pred, float* __restrict__ lat, float* __restrict__ x0_prev,
+                             T* __restrict__ model_in, int64_t n, float guidance, const float* __restrict__ coef,
+                             int64_t coef_stride, const int32_t* __restrict__ keep, int64_t group_elems) {
+    const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    const int64_t g = i / group_elems;                           // group_elems % 4 == 0: the four elements share a group
+    const float* cg = coef + g * coef_stride;
+    const float kx = cg[0], ko = cg[1], A = cg[2], B = cg[3], Cc = cg[4];
+    float u[4], c[4];
+    if constexpr (sizeof(T) == 4) {
+        const float4 a = *(const float4*)(pred + i), b = *(const float4*)(pred + n + i);
+        u[0] = a.x; u[1] = a.y; u[2] = a.z; u[3] = a.w; c[0] = b.x; c[1] = b.y; c[2] = b.z; c[3] = b.w;
+    } else {
+        unpack4(*(const uint2*)(pred + i), u);
+        unpack4(*(const uint2*)(pred + n + i), c);
+    }
+    const float4 l = *(const float4*)(lat + i);
+    const float4 pv = *(const float4*)(x0_prev + i);
+    const float x[4] = {l.x, l.y, l.z, l.w}, pr[4] = {pv.x, pv.y, pv.z, pv.w};
+    float o[4], z[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        z[j] = kx * x[j] + ko * (u[j] + guidance * (c[j] - u[j]));
+        o[j] = A * x[j] + B * z[j] + Cc * pr[j];
+    }
+    *(float4*)(lat + i) = make_float4(o[0], o[1], o[2], o[3]);
+    *(float4*)(x0_prev + i) = make_float4(z[0], z[1], z[2], z[3]);
+    if (model_in && !(keep != nullptr && keep[g] != 0)) {
+        if constexpr (sizeof(T) == 4) {
+            *(float4*)(model_in + i) = make_float4(o[0], o[1], o[2], o[3]);
+            *(float4*)(model_in + n + i) = make_float4(o[0], o[1], o[2], o[3]);
+        } else {
+            const uint2 b = pack4(o);
+            *(uint2*)(model_in + i) = b;
+            *(uint2*)(model_in + n + i) = b;
+        }
+    }
+}
+
 // per-frame affine combination of two fp32 tensors (coefficients per group of `group_elems` consecutive elements):
 //   out = c[g][0] * x + c[g][1] * y      - DDPMScheduler.add_noise / get_velocity with a timestep per (sample, frame, view)
 //   (src/dwm/schedulers/temporal_independent.py:8-45)
@@ -149,13 +194,17 @@ frame_affine_kernel(const float* __restrict__ x, const float* __restrict__ y, co
 //   coef[g] = { sqrt(a_t), sqrt(1 - a_t), sqrt(a_prev), sqrt(1 - a_prev - std^2), std, 0 }
 //   m = u + g (c - u) | u;   (x0, eps) from (sample, m) by prediction type;   x0 clipped;   eps re-derived if asked;
 //   prev = sqrt(a_prev) x0 + dir eps + std noise
+// skip (may be null): one int32 per group, see dwm_cfg_ddim_step_masked
 template <typename PT>
 __global__ void __launch_bounds__(256)
 cfg_ddim_kernel(const PT* __restrict__ pred, int64_t cond_offset, float* __restrict__ lat, bf16_t* __restrict__ model_in,
                 float* __restrict__ x0_out, const float* __restrict__ noise, const float* __restrict__ coef, int64_t n,
-                int64_t group_elems, float guidance, int ptype, float clip, int use_clipped) {
+                int64_t group_elems, float guidance, int ptype, float clip, int use_clipped, const int32_t* __restrict__ skip) {
     const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i >= n) return;
+    // skip[g] != 0: the group keeps latents, x0_out and model_in as they are - the `torch.where(in_schedule_range, ...)` of
+    // diffusion forcing (ctsd.py:1565-1572) and the reference frames of the full-sequence mode
+    if (skip != nullptr && skip[i / group_elems] != 0) return;
     const float* cg = coef + 6 * (i / group_elems);
     const float sa = cg[0], sb = cg[1], sap = cg[2], dir = cg[3], sd = cg[4];
     float m[4];
@@ -431,6 +480,36 @@ extern "C" int dwm_cfg_multistep_f32(const float* pred, float* latents, float* x
     return dwm_launch_status();
 }
 
+// one launcher for both precisions of dwm_cfg_multistep_grouped*
+template <typename T>
+static int cfg_multistep_grouped(const T* pred, float* latents, float* x0_prev, T* model_in, int64_t n, float guidance,
+                                 const float* coef, int64_t coef_rows, const int32_t* keep_model_in, int64_t group_elems,
+                                 void* stream) {
+    if (pred == nullptr || latents == nullptr || x0_prev == nullptr || coef == nullptr || n <= 0 || group_elems <= 0) return DWM_EINVAL;
+    if (n % 4 != 0 || group_elems % 4 != 0 || n % group_elems != 0) return DWM_EALIGN;
+    if (coef_rows != 1 && coef_rows != n / group_elems) return DWM_EINVAL;
+    const uintptr_t amask = sizeof(T) == 4 ? 15u : 7u;
+    if ((((uintptr_t)pred) & amask) || !dwm_aligned16(latents) || !dwm_aligned16(x0_prev) || (model_in && (((uintptr_t)model_in) & amask)) ||
+        (((uintptr_t)coef) & 3u) || (((uintptr_t)keep_model_in) & 3u))
+        return DWM_EALIGN;
+    hipLaunchKernelGGL(cfg_multistep_grouped_kernel<T>, dim3(blocks_for(n / 4)), dim3(256), 0, (hipStream_t)stream, pred, latents,
+                       x0_prev, model_in, n, guidance, coef, (int64_t)(coef_rows == 1 ? 0 : 5), keep_model_in, group_elems);
+    return dwm_launch_status();
+}
+
+extern "C" int dwm_cfg_multistep_grouped(const void* pred, float* latents, float* x0_prev, void* model_in, int64_t n, float guidance,
+                                         const float* coef, int64_t coef_rows, const int32_t* keep_model_in, int64_t group_elems,
+                                         void* stream) {
+    return cfg_multistep_grouped((const bf16_t*)pred, latents, x0_prev, (bf16_t*)model_in, n, guidance, coef, coef_rows, keep_model_in,
+                                 group_elems, stream);
+}
+
+extern "C" int dwm_cfg_multistep_grouped_f32(const float* pred, float* latents, float* x0_prev, float* model_in, int64_t n,
+                                             float guidance, const float* coef, int64_t coef_rows, const int32_t* keep_model_in,
+                                             int64_t group_elems, void* stream) {
+    return cfg_multistep_grouped(pred, latents, x0_prev, model_in, n, guidance, coef, coef_rows, keep_model_in, group_elems, stream);
+}
+
 extern "C" int dwm_frame_affine(const float* x, const float* y, const float* coef, float* out, void* out_bf16, int64_t n,
                                 int64_t group_elems, void* stream) {
     if (x == nullptr || y == nullptr || coef == nullptr || (out == nullptr && out_bf16 == nullptr) || n <= 0 || group_elems <= 0) return DWM_EINVAL;
@@ -445,21 +524,29 @@ extern "C" int dwm_frame_affine(const float* x, const float* y, const float* coe
 extern "C" int dwm_cfg_ddim_step(const void* pred, int32_t pred_is_f32, int32_t cfg, float* latents, void* model_in, float* x0_out,
                                  const float* noise, const float* coef, int64_t n, int64_t group_elems, float guidance,
                                  int32_t prediction_type, float clip_range, int32_t use_clipped_model_output, void* stream) {
+    return dwm_cfg_ddim_step_masked(pred, pred_is_f32, cfg, latents, model_in, x0_out, noise, coef, n, group_elems, guidance,
+                                    prediction_type, clip_range, use_clipped_model_output, nullptr, stream);
+}
+
+extern "C" int dwm_cfg_ddim_step_masked(const void* pred, int32_t pred_is_f32, int32_t cfg, float* latents, void* model_in,
+                                        float* x0_out, const float* noise, const float* coef, int64_t n, int64_t group_elems,
+                                        float guidance, int32_t prediction_type, float clip_range,
+                                        int32_t use_clipped_model_output, const int32_t* skip, void* stream) {
     if (pred == nullptr || latents == nullptr || coef == nullptr || n <= 0 || group_elems <= 0) return DWM_EINVAL;
     if (prediction_type < 0 || prediction_type > 2) return DWM_EINVAL;
     if (n % 4 != 0 || group_elems % 4 != 0 || n % group_elems != 0 || !dwm_aligned16(latents) || (x0_out && !dwm_aligned16(x0_out)) ||
         (noise && !dwm_aligned16(noise)) || (model_in && (((uintptr_t)model_in) & 7u)) ||
-        (((uintptr_t)pred) & (pred_is_f32 ? 15u : 7u)))
+        (((uintptr_t)pred) & (pred_is_f32 ? 15u : 7u)) || (((uintptr_t)skip) & 3u))
         return DWM_EALIGN;
     const int64_t off = cfg ? n : 0;
     if (pred_is_f32)
         hipLaunchKernelGGL(cfg_ddim_kernel<float>, dim3(blocks_for(n / 4)), dim3(256), 0, (hipStream_t)stream, (const float*)pred, off,
                            latents, (bf16_t*)model_in, x0_out, noise, coef, n, group_elems, guidance, prediction_type, clip_range,
-                           use_clipped_model_output);
+                           use_clipped_model_output, skip);
     else
         hipLaunchKernelGGL(cfg_ddim_kernel<bf16_t>, dim3(blocks_for(n / 4)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)pred, off,
                            latents, (bf16_t*)model_in, x0_out, noise, coef, n, group_elems, guidance, prediction_type, clip_range,
-                           use_clipped_model_output);
+                           use_clipped_model_output, skip);
     return dwm_launch_status();
 }
 

@@ -7,7 +7,8 @@
 
 Both operate on *embedded* conditions (the CFG-doubled model kwargs, time on axis 1: what `get_conditions`,
 ctsd.py:416-453, returns) - text encoders and the dataset stack are outside the hot path.
-The per-window model + scheduler loop is `pipeline.CTSDDenoiser` (HIP kernels through the C ABI); the drivers
+The per-window model + scheduler loop is `pipeline.CTSDDenoiser` (SD 3.5) or, for AutoregressiveDriver, `pipeline.UNetDenoiser`
+(SD 2.1; diffusion forcing with schedulers.DDIMScheduler) - HIP kernels through the C ABI; the drivers
 only plan the windows, carry latents between them (device tensors, no host round trip) and draw the noise
 from the host generator in the reference's order, so a seeded run consumes the same random stream.
 
@@ -146,7 +147,7 @@ class Window:
 
 
 class AutoregressiveDriver:
-    """denoiser: pipeline.CTSDDenoiser-like object with run(latents, conditions, stop=, start=, image_latents=,
+    """denoiser: pipeline.CTSDDenoiser / pipeline.UNetDenoiser, or an object like them, with run(latents, conditions, stop=, start=, image_latents=,
     reference_frame_count=, diffusion_forcing=, take_time=, clear_reference_frame_count=) -> latents.
     decode(latents [B, t, V, C, H, W], diffusion_forcing=bool) -> images with dim 0 = (b t v), e.g. a LatentDecoder;
     defaults to returning the latents flattened the same way, so the driver is usable (and testable) without a VAE."""

@@ -909,6 +909,32 @@ def cfg_multistep(pred: torch.Tensor, latents: torch.Tensor, x0_prev: torch.Tens
           x0_prev.data_ptr(), _p(model_in), n, float(guidance), float(kx), float(ko), float(A), float(B), float(Cc))
 
 
+def cfg_multistep_grouped(pred: torch.Tensor, latents: torch.Tensor, x0_prev: torch.Tensor, guidance: float, coef: torch.Tensor,
+                          group_elems: int, keep_model_in: Optional[torch.Tensor] = None,
+                          model_in: Optional[torch.Tensor] = None) -> None:
+    """cfg_multistep with the (kx, ko, A, B, C) rows in device memory: coef fp32 [n / group_elems, 5], or [1, 5] for every
+    group; keep_model_in int32 [n / group_elems]: groups (reference frames) whose model_in entries stay as they are.  See
+    dwm_cfg_multistep_grouped."""
+    n = latents.numel()
+    if pred.dtype not in (bf16, f32) or pred.numel() != 2 * n or not pred.is_contiguous() or not pred.is_cuda:
+        raise RuntimeError("cfg_multistep_grouped: pred must be contiguous bf16 (fp32: the accuracy path) with 2x the latent elements")
+    for t in (latents, x0_prev):
+        if t.dtype != f32 or not t.is_contiguous() or t.numel() != n or not t.is_cuda:
+            raise RuntimeError("cfg_multistep_grouped: latents / x0_prev must be contiguous fp32 device tensors of the same size")
+    if group_elems <= 0 or group_elems % 4 != 0 or n % group_elems != 0:
+        raise RuntimeError(f"cfg_multistep_grouped: group_elems {group_elems} must be a multiple of 4 that divides the {n} latent elements")
+    groups = n // group_elems
+    if coef.dtype != f32 or not coef.is_contiguous() or not coef.is_cuda or coef.numel() not in (5, 5 * groups):
+        raise RuntimeError("cfg_multistep_grouped: coef must be a contiguous fp32 device tensor [n / group_elems, 5] or [1, 5]")
+    if keep_model_in is not None and (keep_model_in.dtype != torch.int32 or not keep_model_in.is_contiguous() or
+                                      not keep_model_in.is_cuda or keep_model_in.numel() != groups):
+        raise RuntimeError("cfg_multistep_grouped: keep_model_in must be a contiguous int32 device tensor [n / group_elems]")
+    if model_in is not None and (model_in.dtype != pred.dtype or model_in.numel() != 2 * n or not model_in.is_contiguous()):
+        raise RuntimeError("cfg_multistep_grouped: model_in must be contiguous, of pred's dtype and size")
+    _call("dwm_cfg_multistep_grouped_f32" if pred.dtype == f32 else "dwm_cfg_multistep_grouped", pred.data_ptr(), latents.data_ptr(),
+          x0_prev.data_ptr(), _p(model_in), n, float(guidance), coef.data_ptr(), coef.numel() // 5, _p(keep_model_in), group_elems)
+
+
 def ray_features(cam: torch.Tensor, h: int, w: int, ldo: int = 128, dtype: torch.dtype = bf16) -> torch.Tensor:
     """cam fp32 [I, 21] (see dwm_ray_features) -> bf16 (or, the fp32 accuracy path, fp32) [I*h*w, ldo]: RayEncoder's 72
     positional-encoding inputs per token."""
@@ -939,9 +965,11 @@ def frame_affine(x: torch.Tensor, y: torch.Tensor, coef: torch.Tensor, group_ele
 def cfg_ddim_step(pred: torch.Tensor, latents: torch.Tensor, coef: torch.Tensor, group_elems: int, prediction_type: int,
                   guidance: Optional[float] = None, clip_range: float = 0.0, use_clipped_model_output: bool = False,
                   noise: Optional[torch.Tensor] = None, x0_out: Optional[torch.Tensor] = None,
-                  model_in: Optional[torch.Tensor] = None) -> None:
+                  model_in: Optional[torch.Tensor] = None, skip: Optional[torch.Tensor] = None) -> None:
     """[CFG combine +] tensor-timestep DDIM update of `latents` (fp32, in place); see dwm_cfg_ddim_step.
-    guidance None: pred holds n elements; otherwise pred = [uncond; cond] with 2n."""
+    guidance None: pred holds n elements; otherwise pred = [uncond; cond] with 2n.
+    skip: int32 [n / group_elems] - groups with a flag != 0 keep latents / x0_out / model_in bit-unchanged
+    (dwm_cfg_ddim_step_masked); None: every group is updated, through the entry point this wrapper always called."""
     n = latents.numel()
     cfg = guidance is not None
     if pred.dtype not in (bf16, f32) or pred.numel() != (2 * n if cfg else n) or not pred.is_contiguous() or not pred.is_cuda:
@@ -953,9 +981,14 @@ def cfg_ddim_step(pred: torch.Tensor, latents: torch.Tensor, coef: torch.Tensor,
         raise RuntimeError("cfg_ddim_step: coef must be a contiguous fp32 device tensor [n / group_elems, 6]")
     if model_in is not None and (model_in.dtype != bf16 or model_in.numel() != (2 * n if cfg else n) or not model_in.is_contiguous()):
         raise RuntimeError("cfg_ddim_step: model_in must be contiguous bf16")
-    _call("dwm_cfg_ddim_step", pred.data_ptr(), int(pred.dtype == f32), int(cfg), latents.data_ptr(), _p(model_in), _p(x0_out),
-          _p(noise), coef.data_ptr(), n, group_elems, float(guidance or 0.0), int(prediction_type), float(clip_range),
-          int(bool(use_clipped_model_output)))
+    args = (pred.data_ptr(), int(pred.dtype == f32), int(cfg), latents.data_ptr(), _p(model_in), _p(x0_out), _p(noise), coef.data_ptr(),
+            n, group_elems, float(guidance or 0.0), int(prediction_type), float(clip_range), int(bool(use_clipped_model_output)))
+    if skip is None:
+        _call("dwm_cfg_ddim_step", *args)
+        return
+    if skip.dtype != torch.int32 or not skip.is_contiguous() or not skip.is_cuda or skip.numel() * group_elems != n:
+        raise RuntimeError("cfg_ddim_step: skip must be a contiguous int32 device tensor [n / group_elems]")
+    _call("dwm_cfg_ddim_step_masked", *args, skip.data_ptr())
 
 
 def unshuffle_tokens(x: torch.Tensor, r: int, ldo: Optional[int] = None, dtype: torch.dtype = bf16) -> torch.Tensor:

@@ -651,11 +651,46 @@ def dpm_solver_coefficients(sigmas: torch.Tensor, i: int, prediction_type: str):
     return kx, ko, A, -at * e * (1.0 + 0.5 / r0), 0.5 * at * e / r0
 
 
+def dpm_solver_coefficient_table(sigmas: torch.Tensor, prediction_type: str) -> torch.Tensor:
+    """[steps, 5] fp32: row i = dpm_solver_coefficients(sigmas, i, prediction_type) - the per-step numbers of
+    dwm_cfg_multistep_grouped, which reads them from device memory (UNetDenoiser copies the table there once per prepare())."""
+    n = sigmas.numel() - 1
+    return torch.tensor([dpm_solver_coefficients(sigmas, i, prediction_type) for i in range(n)], dtype=torch.float64).float()
+
+
+def diffusion_forcing_tables(inference_steps: int, frames: int, steps_per_inference: int, take_time: int):
+    """Per-frame scheduler indices of the diffusion-forcing mode (ctsd.py:1498-1507, 1565-1570) for the steps i that a call with
+    this `take_time` can run, i0 <= i < i0 + inference_steps with i0 = take_time * steps_per_inference (the emitted queue slot
+    walks the whole schedule over them).  Returns (i0, idx int64 [inference_steps, frames], in_range bool [same]):
+        idx[i - i0, j] = min(i - take_time * spi, max(0, i - j * spi)),    in_range[i - i0, j] = i - j * spi >= 0."""
+    spi = steps_per_inference
+    i0 = take_time * spi
+    i = torch.arange(i0, i0 + inference_steps).view(-1, 1)
+    j = torch.arange(frames).view(1, -1)
+    idx = torch.minimum(i - take_time * spi, torch.clamp(i - j * spi, min=0))
+    return i0, idx, (i - j * spi) >= 0
+
+
 class UNetDenoiser:
-    """Hot loop of inference_pipeline (ctsd.py:1496-1575) for the SD 2.1 configs
+    """Hot loop of inference_pipeline (ctsd.py:1439-1654) for the SD 2.1 configs
     (examples/ctsd_21_6views_*_generation.json: DPMSolverMultistepScheduler, guidance 3, 50 steps): UNet forward at the
     CFG batch + guidance combine + DPM-Solver++(2M) update in one kernel.  latents fp32 [B,T,V,4,H,W]; conditions =
-    CFG-doubled model kwargs (unconditional half first)."""
+    CFG-doubled model kwargs (unconditional half first).
+
+    Modes of inference_pipeline, with the keywords of CTSDDenoiser (what drivers.AutoregressiveDriver calls):
+      * full-sequence denoising from noise (default; ctsd.py:1473-1476, 1509-1511, 1574-1575);
+      * reference frames: `image_latents` + `reference_frame_count` = r - the first r frames of both CFG halves of the model
+        input hold image_latents[:, :r] at timestep 0 on every step (:1514-1526) and the result is
+        cat(image_latents[:, :r], latents[:, r:]) (:1623-1627).  Both schedulers: the update kernels take a flag per
+        (sample, frame, view) image and leave the model input of a flagged image alone;
+      * diffusion forcing, `schedulers.DDIMScheduler` only: per-frame timestep indices min(i - take_time*spi,
+        max(0, i - j*spi)) (:1498-1507), the tensor-timestep DDIM step (:1559-1561, temporal_independent.py:67-170), frames
+        outside the schedule range bit-unchanged (:1565-1572), `image_latents` in place of the start latents (:1470-1471).
+        DPMSolverMultistepScheduler has no tensor-timestep step in the reference either: diffusion forcing, or a start
+        step other than 0, with it is a ValueError.
+    With none of these and the graph off, the step is the scalar-coefficient kernel as before.  In every other case the
+    per-step numbers (timesteps, coefficient rows, flags) are rows of device tables built once per prepare(), so that the
+    step can be captured: `enable_graph()` replays the whole step as one HIP graph, as CTSDDenoiser does."""
 
     def __init__(self, model, guidance_scale: float = 3.0, inference_steps: int = 50, prediction_type: str = "v_prediction",
                  scheduler=None):
@@ -673,12 +708,37 @@ class UNetDenoiser:
             self.timesteps, self.sigmas = scheduler.timesteps.cpu(), None
         else:
             self.timesteps, self.sigmas = dpm_solver_tables(inference_steps)
+        self.use_graph = False
+        self._graph = None
+        self._side = None
 
-    def prepare(self, latents: torch.Tensor, conditions: Dict[str, torch.Tensor]):
+    def _check_mode(self, diffusion_forcing: bool, start: int = 0):
+        if self.scheduler is None and (diffusion_forcing or start != 0):
+            raise ValueError("UNetDenoiser: diffusion forcing / a start step other than 0 needs scheduler=schedulers.DDIMScheduler(): "
+                             "DPM-Solver++(2M) is a multistep solver - it carries the x0 of the previous step and has no "
+                             "tensor-timestep step (the reference's DPMSolverMultistepScheduler has none either)")
+
+    def prepare(self, latents: torch.Tensor, conditions: Dict[str, torch.Tensor], image_latents: Optional[torch.Tensor] = None,
+                reference_frame_count: int = 0, diffusion_forcing: bool = False, take_time: int = 0,
+                clear_reference_frame_count: int = 0):
+        self._check_mode(diffusion_forcing)
+        self._graph = None                                                   # buffers below are re-created: capture again
+        if diffusion_forcing and image_latents is not None:
+            latents, image_latents = image_latents, None                     # ctsd.py:1470-1471
         dev = latents.device
+        B, T, V = latents.shape[:3]
+        self.diffusion_forcing = diffusion_forcing
+        self.ref = reference_frame_count if image_latents is not None else 0
+        if not 0 <= self.ref <= T:
+            raise ValueError(f"UNetDenoiser: reference_frame_count {reference_frame_count} outside the {T} frames of the window")
+        if diffusion_forcing:
+            if self.inference_steps % (T - clear_reference_frame_count) != 0:
+                raise ValueError("inference_steps must be a multiple of the frame count in diffusion-forcing mode")
+        self._spi = self.inference_steps // (T - clear_reference_frame_count) if diffusion_forcing else 0
+        self._take_time = take_time
         self.latents = latents.to(torch.float32).contiguous().clone()        # init_noise_sigma = 1
         self.x0_prev = torch.zeros_like(self.latents)
-        B = latents.shape[0]
+        self.image_latents = None if image_latents is None else image_latents.to(device=dev, dtype=torch.float32)
         # model input / conditions / prediction in the model's compute dtype: bf16, or fp32 for the accuracy path
         # (`model.compute_dtype = torch.float32`: BASELINE.json configs[0], the reference's fp32 denoise)
         self.cd = cd = getattr(self.model, "compute_dtype", bf16)
@@ -686,6 +746,10 @@ class UNetDenoiser:
         lat16 = self.latents if cd == torch.float32 else ops.cast_bf16(self.latents)
         self.model_in[:B].copy_(lat16)
         self.model_in[B:].copy_(lat16)
+        if self.ref > 0:                                                     # clean reference frames: written once, the update
+            r16 = self.image_latents[:, :self.ref].to(cd)                    # kernels leave them alone (ctsd.py:1514-1519)
+            self.model_in[:B, :self.ref].copy_(r16)
+            self.model_in[B:, :self.ref].copy_(r16)
         self.conditions = {k: (v.to(cd) if torch.is_tensor(v) and v.is_floating_point() and k != "added_time_ids" else v)
                            for k, v in conditions.items()}
         self._ts = self.timesteps.to(dev).float()
@@ -694,21 +758,66 @@ class UNetDenoiser:
         self._ddim_coef = None
         if self.scheduler is not None:
             self._ddim_coef = self.scheduler.coefficients(self.timesteps.to(dev))
+        # reference frames / diffusion forcing / graph: timesteps, coefficient rows and flags of every step as device tables
+        self._tables = self._step_tables() if (self.ref > 0 or diffusion_forcing or self.use_graph) else None
         return self
 
-    def step(self, i: int):
-        B, T, V = self.latents.shape[:3]
-        ts = self._ts[i].expand(2 * B, T, V)
-        out = self.model(self.model_in, ts, **self.conditions)
-        pred = out["noise_pred"] if isinstance(out, dict) else out[0][0]
+    def _step_tables(self):
+        """(first step, timesteps fp32 [n, 2B, T, V], coefficient rows fp32 [n, G | 1, 6 | 5], flags int32 [n, G] or None) with
+        G = B T V groups in (sample, frame, view) order; row k serves step first + k"""
+        (B, T, V), dev = self.latents.shape[:3], self.latents.device
+        n, G = self.inference_steps, B * T * V
+        first, flags = 0, None
+        if self.diffusion_forcing:
+            first, idx, in_range = diffusion_forcing_tables(n, T, self._spi, self._take_time)
+            t_frame = self.timesteps[idx].to(dev)                                           # [n, T] integer timesteps
+            flags = (~in_range).to(dev)
+        else:
+            t_frame = self.timesteps.to(dev).view(n, 1).repeat(1, T)
+            if self.ref > 0:
+                flags = (torch.arange(T) < self.ref).view(1, T).expand(n, T).to(dev)
+        ts = t_frame.float()
+        if self.ref > 0:
+            ts[:, :self.ref] = 0                                                            # ctsd.py:1520-1526
+        ts = ts.view(n, 1, T, 1).expand(n, 2 * B, T, V).contiguous()
+        if flags is not None:
+            flags = flags.view(n, 1, T, 1).expand(n, B, T, V).reshape(n, G).to(torch.int32).contiguous()
         if self.scheduler is not None:
-            from .schedulers import PREDICTION_TYPES
-            sc = self.scheduler
+            coef = self.scheduler.coefficients(t_frame).view(n, 1, T, 1, 6).expand(n, B, T, V, 6).reshape(n, G, 6).contiguous()
+        else:
+            coef = dpm_solver_coefficient_table(self.sigmas, self.prediction_type).to(dev).view(n, 1, 5)
+        return first, ts, coef, flags
+
+    def _prediction(self, ts: torch.Tensor) -> torch.Tensor:
+        out = self.model(self.model_in, ts, **self.conditions)
+        return out["noise_pred"] if isinstance(out, dict) else out[0][0]
+
+    def _ddim_args(self):
+        from .schedulers import PREDICTION_TYPES
+        sc = self.scheduler
+        return dict(group_elems=self.latents[0, 0, 0].numel(), prediction_type=PREDICTION_TYPES[sc.config.prediction_type],
+                    guidance=self.guidance_scale, clip_range=sc.config.clip_sample_range if sc.config.clip_sample else 0.0)
+
+    def step(self, i: int):
+        if self._tables is None and self.use_graph:   # enable_graph() after prepare()
+            self._tables = self._step_tables()
+        if self._tables is not None:
+            k = i - self._tables[0]
+            if not 0 <= k < self.inference_steps:
+                raise ValueError(f"UNetDenoiser: step {i} outside the steps [{self._tables[0]}, {self._tables[0] + self.inference_steps}) "
+                                 "this prepare() serves")
+            if self.use_graph:
+                self._graph_step(k)
+            else:
+                _, ts, coef, flags = self._tables
+                self._step_body(ts[k], coef[k], None if flags is None else flags[k])
+            return
+        B, T, V = self.latents.shape[:3]
+        pred = self._prediction(self._ts[i].expand(2 * B, T, V))
+        if self.scheduler is not None:
             coef = self._ddim_coef[i].expand(B * T * V, 6).contiguous()
             f32_path = self.cd == torch.float32       # (the kernel writes a bf16 model input; the fp32 path copies the latents)
-            ops.cfg_ddim_step(pred, self.latents, coef, self.latents[0, 0, 0].numel(), PREDICTION_TYPES[sc.config.prediction_type],
-                              guidance=self.guidance_scale, clip_range=sc.config.clip_sample_range if sc.config.clip_sample else 0.0,
-                              model_in=None if f32_path else self.model_in)
+            ops.cfg_ddim_step(pred, self.latents, coef, model_in=None if f32_path else self.model_in, **self._ddim_args())
             if f32_path:
                 self.model_in[:B].copy_(self.latents)
                 self.model_in[B:].copy_(self.latents)
@@ -716,8 +825,62 @@ class UNetDenoiser:
         kx, ko, A, Bc, Cc = dpm_solver_coefficients(self.sigmas, i, self.prediction_type)
         ops.cfg_multistep(pred, self.latents, self.x0_prev, self.guidance_scale, kx, ko, A, Bc, Cc, model_in=self.model_in)
 
-    def run(self, latents, conditions, stop: Optional[int] = None):
-        self.prepare(latents, conditions)
-        for i in range(self.inference_steps if stop is None else stop):
-            self.step(i)
+    def _step_body(self, ts: torch.Tensor, coef: torch.Tensor, flags: Optional[torch.Tensor]):
+        """one step from device-resident per-step numbers: nothing here reads a device value on the host, so it can be captured"""
+        B, r = self.latents.shape[0], self.ref
+        pred = self._prediction(ts)
+        if self.scheduler is None:
+            ops.cfg_multistep_grouped(pred, self.latents, self.x0_prev, self.guidance_scale, coef, self.latents[0, 0, 0].numel(),
+                                      keep_model_in=flags, model_in=self.model_in)
+            return
+        f32_path = self.cd == torch.float32           # (as in step(): the DDIM kernel writes a bf16 model input only)
+        ops.cfg_ddim_step(pred, self.latents, coef, model_in=None if f32_path else self.model_in, skip=flags, **self._ddim_args())
+        if f32_path:                                  # the reference frames of the model input stay the clean ones
+            self.model_in[:B, r:].copy_(self.latents[:, r:])
+            self.model_in[B:, r:].copy_(self.latents[:, r:])
+
+    # ---- whole-step HIP graph, as CTSDDenoiser's: the launches of one step (UNet forward, CFG combine, scheduler update) are
+    # captured once per prepare() and replayed; timesteps, coefficient rows and flags live in static device buffers that are
+    # refreshed (device-to-device, from the tables of prepare()) before each replay.
+    def enable_graph(self, on: bool = True):
+        self.use_graph = on
+        self._graph = None
+        return self
+
+    def _graph_step(self, k: int):
+        _, ts, coef, flags = self._tables
+        if self._graph is None:
+            self._g_ts, self._g_coef = ts[k].clone(), coef[k].clone()
+            self._g_flags = None if flags is None else flags[k].clone()
+            # one eager pass on a side stream fills every cache the forward keeps (packed weights, text K/V, index embeddings,
+            # scratch buffers) and warms the allocator; the state it touched is restored before the capture
+            keep = [t.clone() for t in (self.latents, self.x0_prev, self.model_in)]
+            if self._side is None:
+                self._side = torch.cuda.Stream(device=self.latents.device)
+            side = self._side
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self._step_body(self._g_ts, self._g_coef, self._g_flags)
+            torch.cuda.current_stream().wait_stream(side)
+            for t, k0 in zip((self.latents, self.x0_prev, self.model_in), keep):
+                t.copy_(k0)
+            self._graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self._graph):
+                self._step_body(self._g_ts, self._g_coef, self._g_flags)
+        self._g_ts.copy_(ts[k])
+        self._g_coef.copy_(coef[k])
+        if flags is not None:
+            self._g_flags.copy_(flags[k])
+        self._graph.replay()
+
+    def result(self) -> torch.Tensor:
+        if self.ref > 0:                                                     # ctsd.py:1623-1627
+            return torch.cat([self.image_latents[:, :self.ref], self.latents[:, self.ref:]], 1)
         return self.latents
+
+    def run(self, latents, conditions, stop: Optional[int] = None, start: int = 0, **prepare_kw):
+        self._check_mode(prepare_kw.get("diffusion_forcing", False), start)
+        self.prepare(latents, conditions, **prepare_kw)
+        for i in range(start, self.inference_steps if stop is None else stop):
+            self.step(i)
+        return self.result()
