@@ -514,12 +514,18 @@ int dwm_segsum_diff(const void* a, int64_t lda, const void* b, int64_t ldb, cons
 /* y = act(x) / dx = dy * act'(x); act = DWM_ACT_GELU_TANH | DWM_ACT_SILU; n % 8 == 0 */
 int dwm_act_fwd(const void* x, void* y, int64_t n, int32_t act, void* stream);
 int dwm_act_bwd(const void* x, const void* dy, void* dx, int64_t n, int32_t act, void* stream);
+/* dwm_act_fwd and dwm_act_bwd from one read of x: y_out = act(x), dx = dy * act'(x), each bit-equal to what the separate
+ * calls write.  For a backward that did not keep act(x) and needs it for the next weight gradient. */
+int dwm_act_bwd_recompute(const void* x, const void* dy, void* y_out, void* dx, int64_t n, int32_t act, void* stream);
 
 /* diffusers GEGLU on the un-packed projection u [rows, 2*inner] = [value | gate]:
  * g = value * gelu(gate) (erf form);  du = [dg * gelu(gate) | dg * value * gelu'(gate)] */
 int dwm_geglu_fwd(const void* u, int64_t ldu, int64_t rows, int64_t inner, void* g, int64_t ldg, void* stream);
 int dwm_geglu_bwd(const void* u, int64_t ldu, const void* dg, int64_t lddg, int64_t rows, int64_t inner,
                   void* du, int64_t lddu, void* stream);
+/* dwm_geglu_fwd and dwm_geglu_bwd from one read of u: g_out [rows, inner] = value * gelu(gate), du as dwm_geglu_bwd writes it */
+int dwm_geglu_bwd_recompute(const void* u, int64_t ldu, const void* dg, int64_t lddg, int64_t rows, int64_t inner,
+                            void* g_out, int64_t ldg, void* du, int64_t lddu, void* stream);
 
 /* out[r, n] = a[r, n] * (gate_a ? gate_a[r / rows_per_gate_a, n] : 1) * (coef_a ? coef_a[r / rows_per_coef_a] : 1)
  *           + (b ? b[r, n] * (coef_b ? coef_b[r / rows_per_coef_b] : 1) : 0)

@@ -193,6 +193,8 @@ SIGNATURES = {
     "dwm_act_bwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp]),
     "dwm_geglu_fwd": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _vp]),
     "dwm_geglu_bwd": (_i32, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp]),
+    "dwm_act_bwd_recompute": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "dwm_geglu_bwd_recompute": (_i32, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "dwm_rowcombine": (_i32, [C.POINTER(RowCombineArgs), _vp]),
     "dwm_layernorm_bwd": (_i32, [C.POINTER(LayerNormBwdArgs), _vp]),
     "dwm_rmsnorm_heads_train": (_i32, [_vp, _i64, _i64, _i64, _vp, _f32, _vp, _vp]),

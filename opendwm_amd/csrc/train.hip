@@ -140,6 +140,27 @@ act_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy, bf16_t* 
     }
 }
 
+// Backward that also re-derives the activation it differentiates: y = act(x), dx = dy * act'(x) from one read of x.  The two results
+// come from the expressions of act_kernel<ACT, false> and act_kernel<ACT, true>, so they are the values those kernels write.
+template <int ACT>
+__global__ void __launch_bounds__(256)
+act_bwd_recompute_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy, bf16_t* __restrict__ y, bf16_t* __restrict__ dx,
+                         int64_t n8) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
+        float v[8], d[8], o[8];
+        unpack8(*(const uint4*)(x + i * 8), v);
+        unpack8(*(const uint4*)(dy + i * 8), d);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            o[j] = ACT == DWM_ACT_GELU_TANH ? gelu_tanh_f(v[j]) : ACT == DWM_ACT_RELU ? fmaxf(v[j], 0.f) : silu_f(v[j]);
+            d[j] = ACT == DWM_ACT_RELU ? (v[j] > 0.f ? d[j] : 0.f)
+                                       : d[j] * (ACT == DWM_ACT_GELU_TANH ? gelu_tanh_grad(v[j]) : silu_grad(v[j]));
+        }
+        *(uint4*)(y + i * 8) = pack8(o);
+        *(uint4*)(dx + i * 8) = pack8(d);
+    }
+}
+
 // GEGLU: u [rows, 2*inner] = [value | gate];  g = value * gelu_erf(gate)
 template <bool BWD>
 __global__ void __launch_bounds__(256)
@@ -167,6 +188,29 @@ geglu_kernel(const bf16_t* __restrict__ u, int64_t ldu, const bf16_t* __restrict
             *(uint4*)(out + r * ldo + c) = pack8(dv);
             *(uint4*)(out + r * ldo + inner + c) = pack8(dgt);
         }
+    }
+}
+
+// geglu_kernel<true> that also writes g = value * gelu(gate), the operand of the second linear's weight gradient
+__global__ void __launch_bounds__(256)
+geglu_bwd_recompute_kernel(const bf16_t* __restrict__ u, int64_t ldu, const bf16_t* __restrict__ dg, int64_t lddg,
+                           bf16_t* __restrict__ g, int64_t ldg, bf16_t* __restrict__ du, int64_t lddu, int64_t rows, int64_t inner) {
+    const int64_t c8 = inner / 8, total = rows * c8;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = i / c8, c = (i - r * c8) * 8;
+        float hv[8], gt[8], d[8], o[8], dv[8], dgt[8];
+        unpack8(*(const uint4*)(u + r * ldu + c), hv);
+        unpack8(*(const uint4*)(u + r * ldu + inner + c), gt);
+        unpack8(*(const uint4*)(dg + r * lddg + c), d);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            o[j] = hv[j] * gelu_erf_f(gt[j]);
+            dv[j] = d[j] * gelu_erf_f(gt[j]);
+            dgt[j] = d[j] * hv[j] * gelu_erf_grad(gt[j]);
+        }
+        *(uint4*)(g + r * ldg + c) = pack8(o);
+        *(uint4*)(du + r * lddu + c) = pack8(dv);
+        *(uint4*)(du + r * lddu + inner + c) = pack8(dgt);
     }
 }
 
@@ -776,6 +820,17 @@ extern "C" int dwm_act_bwd(const void* x, const void* dy, void* dx, int64_t n, i
     return dwm_launch_status();
 }
 
+extern "C" int dwm_act_bwd_recompute(const void* x, const void* dy, void* y_out, void* dx, int64_t n, int32_t act, void* stream) {
+    if (!x || !dy || !y_out || !dx || n <= 0 || n % 8 != 0) return DWM_EINVAL;
+    if (!dwm_aligned16(x) || !dwm_aligned16(dy) || !dwm_aligned16(y_out) || !dwm_aligned16(dx)) return DWM_EALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    if (act == DWM_ACT_GELU_TANH) hipLaunchKernelGGL((act_bwd_recompute_kernel<DWM_ACT_GELU_TANH>), dim3(grid_for(n / 8)), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)y_out, (bf16_t*)dx, n / 8);
+    else if (act == DWM_ACT_SILU) hipLaunchKernelGGL((act_bwd_recompute_kernel<DWM_ACT_SILU>), dim3(grid_for(n / 8)), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)y_out, (bf16_t*)dx, n / 8);
+    else if (act == DWM_ACT_RELU) hipLaunchKernelGGL((act_bwd_recompute_kernel<DWM_ACT_RELU>), dim3(grid_for(n / 8)), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)y_out, (bf16_t*)dx, n / 8);
+    else return DWM_EINVAL;
+    return dwm_launch_status();
+}
+
 extern "C" int dwm_geglu_fwd(const void* u, int64_t ldu, int64_t rows, int64_t inner, void* g, int64_t ldg, void* stream) {
     if (!u || !g || rows <= 0 || inner <= 0 || inner % 8 != 0 || ldu < 2 * inner || ldg < inner) return DWM_EINVAL;
     if (ldu % 8 != 0 || ldg % 8 != 0 || !dwm_aligned16(u) || !dwm_aligned16(g)) return DWM_EALIGN;
@@ -790,6 +845,17 @@ extern "C" int dwm_geglu_bwd(const void* u, int64_t ldu, const void* dg, int64_t
     if (ldu % 8 != 0 || lddg % 8 != 0 || lddu % 8 != 0 || !dwm_aligned16(u) || !dwm_aligned16(dg) || !dwm_aligned16(du)) return DWM_EALIGN;
     hipLaunchKernelGGL((geglu_kernel<true>), dim3(grid_for(rows * inner / 8)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)u, ldu, (const bf16_t*)dg, lddg, (bf16_t*)du, lddu, rows, inner);
+    return dwm_launch_status();
+}
+
+extern "C" int dwm_geglu_bwd_recompute(const void* u, int64_t ldu, const void* dg, int64_t lddg, int64_t rows, int64_t inner,
+                                       void* g_out, int64_t ldg, void* du, int64_t lddu, void* stream) {
+    if (!u || !dg || !g_out || !du || rows <= 0 || inner <= 0 || inner % 8 != 0 || ldu < 2 * inner || lddg < inner || ldg < inner ||
+        lddu < 2 * inner) return DWM_EINVAL;
+    if (ldu % 8 != 0 || lddg % 8 != 0 || ldg % 8 != 0 || lddu % 8 != 0 || !dwm_aligned16(u) || !dwm_aligned16(dg) ||
+        !dwm_aligned16(g_out) || !dwm_aligned16(du)) return DWM_EALIGN;
+    hipLaunchKernelGGL(geglu_bwd_recompute_kernel, dim3(grid_for(rows * inner / 8)), dim3(256), 0, (hipStream_t)stream,
+                       (const bf16_t*)u, ldu, (const bf16_t*)dg, lddg, (bf16_t*)g_out, ldg, (bf16_t*)du, lddu, rows, inner);
     return dwm_launch_status();
 }
 

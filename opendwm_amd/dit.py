@@ -140,6 +140,14 @@ class RayEncoder(nn.Module):
 
 
 class DiTCrossviewTemporalConditionModel(_Base):
+    # How the training forward treats block activations (opendwm_amd.train.resolve_activation_policy): "recompute" (every block is
+    # gradient-checkpointed), "keep", or "config" (gradient_checkpointing / temporal_ / crossview_gradient_checkpointing decide per
+    # family).  Plain attributes, set by CTSDTrainer(activations=..., activation_budget_gib=...): neither constructor arguments nor
+    # part of the config or the state dict.  activation_plan: the train.ActivationPlan of the last training forward.
+    activation_policy = "recompute"
+    activation_budget_gib = None
+    activation_plan = None
+
     def __init__(
         self,
         patch_size: int = 2,
@@ -307,7 +315,7 @@ class DiTCrossviewTemporalConditionModel(_Base):
     # ---- forward (crossview_temporal_dit.py:372-630)
     def forward(self, sample, timestep=None, *args, **kwargs):
         """Reference signature.  In train() mode with autograd enabled the prediction carries a grad_fn
-        (opendwm_amd.train: checkpointed block Functions with HIP backward kernels); otherwise the fused
+        (opendwm_amd.train: block Functions with HIP backward kernels, checkpointed unless activation_policy keeps them); otherwise the fused
         inference path runs under no_grad."""
         if self.training and torch.is_grad_enabled():
             from . import train as _train

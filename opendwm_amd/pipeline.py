@@ -363,7 +363,8 @@ class CTSDTrainer:
                  max_grad_norm: Optional[float] = None, weighting_scheme: str = "logit_normal", ddp: bool = False,
                  ddp_kwargs: Optional[dict] = None, common_config: Optional[dict] = None, training_config: Optional[dict] = None,
                  reference_latent_count=0, lr_scheduler=None, ddp_comm_dtype: Optional[torch.dtype] = None,
-                 train_scheduler=None, optimizer_bits: int = 32, grad_conditioning: str = "torch"):
+                 train_scheduler=None, optimizer_bits: int = 32, grad_conditioning: str = "torch",
+                 activations: str = "recompute", activation_budget_gib: Optional[float] = None):
         """common_config["frame_prediction_style"] (None | "diffusion_forcing" | "ctsd") and training_config select the
         training task mix of `make_input_for_prediction`; with "diffusion_forcing" every frame draws its own timestep
         (ctsd.py:1232-1237).  optimizer_bits: 32 = train.AdamW (fp32 moments), 8 = train.AdamW8bit (block-wise 8-bit moments: the
@@ -374,8 +375,27 @@ class CTSDTrainer:
         grad_scale; the gradients are never rewritten, the loss scale is a train.LossScaler (GradScaler's dynamics and state dict),
         `last_grad_norm` / `skipped_steps` are kept for logging.  One deviation from the reference's control flow, in this mode
         only: with a clip but NO scaler a step whose gradients hold an inf / nan is skipped (with one warning) - the torch route
-        clips by a nan coefficient there and writes nan into every weight."""
+        clips by a nan coefficient there and writes nan into every weight.
+        activations (MMDiT only): what the transformer blocks hold between forward and backward.  "recompute" (default): the block
+        inputs - every block is gradient-checkpointed and its backward runs its forward again.  "keep": every joint block and every
+        cross-view / temporal block keeps its activations (train.kept_bytes) and skips the recompute.  "config": per family, as the
+        reference's switches say - joint blocks recompute iff model.gradient_checkpointing, temporal blocks iff
+        temporal_gradient_checkpointing, cross-view blocks iff crossview_gradient_checkpointing.  activation_budget_gib caps the
+        kept bytes of one forward: blocks are visited in forward order and one that does not fit in what is left recomputes
+        (0: nothing is kept, None: no cap).  `activation_plan` reports the decisions of the last forward."""
         from . import train as _train
+        from .unet import UNetCrossviewTemporalConditionModel
+        if activations not in _train.ACTIVATION_POLICIES:
+            raise ValueError(f"activations: one of {_train.ACTIVATION_POLICIES}, got {activations!r}")
+        if activation_budget_gib is not None and activation_budget_gib < 0:
+            raise ValueError(f"activation_budget_gib: None or >= 0, got {activation_budget_gib!r}")
+        self.is_unet = isinstance(model, UNetCrossviewTemporalConditionModel)
+        if self.is_unet and activations != "recompute":
+            raise NotImplementedError(f"activations={activations!r} with the SD 2.1 UNet: its ResNet / transformer Functions "
+                                      "(train_unet) have no kept-activation form yet, only the MMDiT blocks do")
+        self.activations, self.activation_budget_gib = activations, activation_budget_gib
+        if not self.is_unet:
+            model.activation_policy, model.activation_budget_gib = activations, activation_budget_gib
         if optimizer_bits not in (8, 32):
             raise ValueError(f"optimizer_bits: 8 or 32, got {optimizer_bits!r}")
         if grad_conditioning not in ("torch", "fused"):
@@ -425,12 +445,16 @@ class CTSDTrainer:
         self.weighting_scheme = weighting_scheme
         self.reference_latent_count = reference_latent_count
         # SD 2.1 branch (ctsd.py:1240-1253): the model is the UNet -> DDPM noising, epsilon / v_prediction target
-        from .unet import UNetCrossviewTemporalConditionModel
-        self.is_unet = isinstance(model, UNetCrossviewTemporalConditionModel)
         if self.is_unet and train_scheduler is None:
             from .schedulers import DDPMScheduler
             train_scheduler = DDPMScheduler(num_train_timesteps=num_train_timesteps)
         self.train_scheduler = train_scheduler
+
+    @property
+    def activation_plan(self):
+        """train.ActivationPlan of the last training forward: `.blocks` = (block name, "keep" | "recompute", kept bytes) per
+        transformer block in forward order, `.total_bytes` their sum; None before the first forward"""
+        return getattr(self.model, "activation_plan", None)
 
     def draw_condition_masks(self, batch_size: int, generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
         """the per-sample condition dropout masks of the training step in the reference's draw order (ctsd.py:1278-1301):
@@ -526,6 +550,8 @@ class CTSDTrainer:
                 for k, v in conditions.items()}
         if extra is not None:
             cond.update(extra)
+        if hasattr(self, "activations"):        # this trainer's policy holds for its forwards (trainers may share a model)
+            self.model.activation_policy, self.model.activation_budget_gib = self.activations, self.activation_budget_gib
         pred = self.wrapper(noisy.to(bf16), timesteps, **cond)[0][0]
         x0_hat, target = pred.float() * (-sig) + noisy, latents.float()
         if self.training_config.get("disable_reference_frame_loss", False):          # ctsd.py:1363-1367

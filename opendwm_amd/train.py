@@ -3,10 +3,12 @@ forward under autocast with gradient checkpointing `:497-521`, `loss.backward()`
 optimizer `:1406-1432`; DDP wrap `:1051-1054`).
 
 Design (MI355X-first rather than op-by-op autograd):
-  * one `torch.autograd.Function` per transformer block.  Its forward is the fused inference path
+  * one `torch.autograd.Function` per transformer block.  By default its forward is the fused inference path
     (opendwm_amd.blocks.*.run) and keeps only the block inputs - the reference's gradient
     checkpointing; its backward re-runs the block un-fused (pre-activations are needed) and then
-    walks it backwards with the hand-written HIP kernels of include/dwm_hip.h "Training".
+    walks it backwards with the hand-written HIP kernels of include/dwm_hip.h "Training".  A block
+    that the model's activation_policy keeps (see "kept activations" below) runs the un-fused
+    training forward as its forward, holds its kept set and goes straight to the backward walk.
   * parameters enter the Functions as inputs, so autograd's AccumulateGrad nodes - and with them
     `DistributedDataParallel`'s bucketed RCCL all-reduce - see every gradient as soon as its block
     is done; torch only orchestrates, all arithmetic on token-sized tensors is HIP.
@@ -149,19 +151,145 @@ def _grads_for(G: Grads, params, needs) -> tuple:
     return tuple((G.take(p) if need else None) for p, need in zip(params, needs))
 
 
+# ------------------------------------------------------------------------------------------ kept activations
+# A block either recomputes (its Function keeps the block inputs and backward runs the training forward first: gradient
+# checkpointing, the default) or keeps (the training forward IS its forward and its kept set stays alive until backward).
+ACTIVATION_POLICIES = ("recompute", "keep", "config")
+
+
+def resolve_activation_policy(policy: str, gradient_checkpointing: bool = False, temporal_gradient_checkpointing: bool = False,
+                              crossview_gradient_checkpointing: bool = False) -> Dict[str, bool]:
+    """block family ("joint" | "temporal" | "crossview") -> True if the policy wants its blocks to keep their activations.
+    "config": the reference's three switches decide, a family recomputes iff its switch is set
+    (crossview_temporal_dit.py:497, :539, :570)."""
+    if policy == "recompute":
+        return {"joint": False, "temporal": False, "crossview": False}
+    if policy == "keep":
+        return {"joint": True, "temporal": True, "crossview": True}
+    if policy == "config":
+        return {"joint": not gradient_checkpointing, "temporal": not temporal_gradient_checkpointing,
+                "crossview": not crossview_gradient_checkpointing}
+    raise ValueError(f"activations: one of {ACTIVATION_POLICIES}, got {policy!r}")
+
+
+class ActivationPlan:
+    """The keep / recompute decisions of one forward.  `blocks`: (block name, "keep" | "recompute", kept bytes) in forward order,
+    `total_bytes`: their sum.  A block that the policy wants kept is kept only while its bytes fit in what is left of the budget
+    (budget_gib None: no cap; 0: nothing is kept); a refused block takes nothing, so a later smaller one may still fit."""
+
+    def __init__(self, budget_gib: Optional[float] = None):
+        if budget_gib is not None and budget_gib < 0:
+            raise ValueError(f"activation_budget_gib: None or >= 0, got {budget_gib!r}")
+        self.blocks: List[tuple] = []
+        self.left: Optional[int] = None if budget_gib is None else int(budget_gib * 2 ** 30)
+
+    def decide(self, name: str, wanted: bool, nbytes: int) -> bool:
+        keep = bool(wanted) and (self.left is None or 0 < nbytes <= self.left)
+        if keep and self.left is not None:
+            self.left -= nbytes
+        self.blocks.append((name, "keep" if keep else "recompute", nbytes if keep else 0))
+        return keep
+
+    @property
+    def total_bytes(self) -> int:
+        return sum(b[2] for b in self.blocks)
+
+    def __iter__(self):
+        return iter(self.blocks)
+
+    def __len__(self):
+        return len(self.blocks)
+
+
+def plan_activations(blocks, budget_gib: Optional[float] = None) -> ActivationPlan:
+    """blocks: (name, wanted by the policy, kept bytes) in forward order -> the plan under the budget"""
+    plan = ActivationPlan(budget_gib)
+    for name, wanted, nbytes in blocks:
+        plan.decide(name, wanted, nbytes)
+    return plan
+
+
+def kept_bytes(kind: str, *, images: int, tokens: int, dim: int, heads: int, context_tokens: int = 0, ff_inner: Optional[int] = None,
+               dual: bool = False, context_pre_only: bool = False, qk_norm: bool = True, emb_rows: int = 0, samples: int = 0,
+               lse_rows: Optional[int] = None) -> int:
+    """Bytes a kept block holds from its forward to its backward: its inputs, the outputs of its GEMM and attention launches with
+    lse and the RMSNorm 1/rms, and the residual-stream values a LayerNorm reads.  LayerNorm and activation outputs are not kept
+    (backward re-derives them), and none of the kept tensors is read by a weight gradient alone, so freezing weights changes the
+    launches of the backward but not this figure.
+    kind "joint": images x tokens sample rows, images x context_tokens context rows, ff_inner the width of the GELU.
+    kind "vt": images x tokens rows, emb_rows embedding rows, samples alpha values, ff_inner the GEGLU output width (the
+    projection is twice as wide), lse_rows = problems x padded problem length of the row map (default: the rows)."""
+    R, Rc, D, H = images * tokens, images * context_tokens, dim, heads
+    F = 4 * dim if ff_inner is None else ff_inner
+    if kind == "joint":
+        b16 = R * D + Rc * D + images * D                                  # h, c, st
+        b16 += images * D * ((9 if dual else 6) + (2 if context_pre_only else 6))   # mod, cmod
+        b16 += 3 * (R + Rc) * D + (R + Rc) * D                             # qkv, cqkv, ao, cao
+        b16 += 2 * R * D + R * F + R * D                                   # t_att, h1, u, t_ff
+        f32 = images * H * (tokens + context_tokens)                       # lse
+        if qk_norm:
+            f32 += 2 * H * (R + Rc)                                        # rinv, crinv
+        if dual:
+            b16 += 3 * R * D + 2 * R * D                                   # qkv2, ao2, t_att2
+            f32 += images * H * tokens + (2 * H * R if qk_norm else 0)     # lse2, rinv2
+        if not context_pre_only:
+            b16 += 3 * Rc * D + Rc * F                                     # t_catt, c1, t_cff, cu
+        return 2 * b16 + 4 * f32
+    if kind == "vt":
+        b16 = R * D + emb_rows * D                                         # h, emb
+        b16 += 2 * (2 * R * F) + 3 * R * D                                 # u1, u3, qkv
+        b16 += 4 * R * D                                                   # xs1, ao, xs2, out
+        f32 = samples + H * (R if lse_rows is None else lse_rows)          # alpha, lse
+        if qk_norm:
+            f32 += 2 * H * R                                               # rinv
+        return 2 * b16 + 4 * f32
+    raise ValueError(f"kept_bytes: kind 'joint' or 'vt', got {kind!r}")
+
+
+def joint_kept_bytes(blk: JointTransformerBlock, h: torch.Tensor, c: torch.Tensor, n_img: int) -> int:
+    return kept_bytes("joint", images=n_img, tokens=h.shape[0] // n_img, context_tokens=c.shape[0] // n_img, dim=blk.dim,
+                      heads=blk.heads, ff_inner=blk.ff.net[2].in_features, dual=blk.use_dual_attention,
+                      context_pre_only=blk.context_pre_only, qk_norm=blk.attn.has_qk_norm)
+
+
+def vt_kept_bytes(blk: VTSelfAttentionBlock, h: torch.Tensor, rowmap, emb: torch.Tensor, alpha: torch.Tensor) -> int:
+    return kept_bytes("vt", images=1, tokens=h.shape[0], dim=blk.dim, heads=blk.heads, ff_inner=blk.ff.net[2].in_features,
+                      qk_norm=blk.attn1.has_qk_norm, emb_rows=emb.shape[0], samples=alpha.numel(),
+                      lse_rows=rowmap.n_problems * rowmap.L0)
+
+
+def _act_lin_bwd(G: Grads, lin2: torch.nn.Linear, pre: torch.Tensor, act_out: Optional[torch.Tensor], dy: torch.Tensor,
+                 act: Optional[int]) -> torch.Tensor:
+    """backward of lin2(a), a = act(pre) (act None: GEGLU) -> d(pre).  act_out = a where the forward kept it; None: backward
+    re-derives it in the pass that differentiates it - input gradient of lin2 first, then ONE read of `pre` for a and d(pre), then
+    the weight gradient of lin2 on a.  The same operands reach the same kernels either way."""
+    if act_out is not None:
+        da = lin_bwd(G, lin2, act_out, dy)
+        return T.geglu_bwd(pre, da) if act is None else T.act_bwd(pre, da, act)
+    da = T.linear_dgrad(dy, w_t(lin2.weight))
+    if not lin2.weight.requires_grad:            # nobody reads a: the one-output kernel
+        dpre = T.geglu_bwd(pre, da) if act is None else T.act_bwd(pre, da, act)
+    else:
+        act_out, dpre = T.geglu_bwd_recompute(pre, da) if act is None else T.act_bwd_recompute(pre, da, act)
+    lin_bwd(G, lin2, act_out, dy, need_dx=False)
+    return dpre
+
+
 # ------------------------------------------------------------------------------------------ joint block
-def joint_block_backward(blk: JointTransformerBlock, h: torch.Tensor, c: torch.Tensor, st: torch.Tensor, n_img: int,
-                         dh: torch.Tensor, dc: Optional[torch.Tensor], G: Grads):
-    """Recompute + backward of JointTransformerBlock.run (diffusers JointTransformerBlock.forward).
-    h [I*N, D], c [I*Lc, D], st = silu(temb) [I, D]: the block INPUTS; dh / dc: gradients of its outputs.
-    Returns (dh_in, dc_in, dst)."""
+def joint_block_forward_train(blk: JointTransformerBlock, h: torch.Tensor, c: torch.Tensor, st: torch.Tensor, n_img: int,
+                              keep: bool = False):
+    """Training forward of JointTransformerBlock.run (diffusers JointTransformerBlock.forward), un-fused where the backward needs
+    a pre-activation.  h [I*N, D], c [I*Lc, D], st = silu(temb) [I, D].  Returns (h_out, c_out, kept).
+    keep=False (the first half of a recomputing backward): kept holds every intermediate and the block outputs are not formed.
+    keep=True (the forward of a kept block): the outputs are formed and kept holds what kept_bytes counts - LayerNorm and
+    activation outputs are dropped, joint_block_backward_kept re-derives them."""
     D = blk.dim
     N, Lc = h.shape[0] // n_img, c.shape[0] // n_img
     dual, pre_only = blk.use_dual_attention, blk.context_pre_only
     sl = lambda m, i: m[:, i * D:(i + 1) * D]
     id_map = ops.rowmap_identity(n_img, N)
+    K: Dict[str, Optional[torch.Tensor]] = dict(h=h, c=c, st=st)
 
-    # ---------------- recompute (un-fused where a pre-activation is needed)
     mod = lin_fwd(st, blk.norm1.linear)
     cmod = lin_fwd(st, blk.norm1_context.linear)
     nh2 = torch.empty_like(h) if dual else None
@@ -177,6 +305,7 @@ def joint_block_backward(blk: JointTransformerBlock, h: torch.Tensor, c: torch.T
                   q1=cqkv[:, :D], k1=cqkv[:, D:2 * D], v1=cqkv[:, 2 * D:], out1=cao, lse=lse)
     t_att = lin_fwd(ao, blk.attn.to_out[0])
     h1 = T.rowcombine(t_att, gate_a=sl(mod, 2), rows_per_gate_a=N, b=h)
+    K.update(mod=mod, cmod=cmod, qkv=qkv, rinv=rinv, cqkv=cqkv, crinv=crinv, ao=ao, cao=cao, lse=lse, t_att=t_att)
     if dual:
         qkv2, rinv2 = project_qkv_train(blk.attn2, nh2)
         ao2 = torch.empty_like(h)
@@ -184,16 +313,17 @@ def joint_block_backward(blk: JointTransformerBlock, h: torch.Tensor, c: torch.T
         ops.attention(qkv2[:, :D], qkv2[:, D:2 * D], qkv2[:, 2 * D:], ao2, id_map, blk.heads, lse=lse2)
         t_att2 = lin_fwd(ao2, blk.attn2.to_out[0])
         h1 = T.rowcombine(t_att2, gate_a=sl(mod, 8), rows_per_gate_a=N, b=h1)
+        K.update(qkv2=qkv2, rinv2=rinv2, ao2=ao2, lse2=lse2, t_att2=t_att2)
     nh3 = ops.layernorm(h1, eps=1e-6, scale=sl(mod, 4), shift=sl(mod, 3), rows_per_mod=N)
     f1, f2 = blk.ff.net[0].proj, blk.ff.net[2]
     u = lin_fwd(nh3, f1)
     ffh = T.act_fwd(u, ACT_GELU_TANH)
     t_ff = lin_fwd(ffh, f2)
-
-    dmod = torch.zeros(mod.shape, dtype=torch.float32, device=h.device)
-    dcmod = torch.zeros(cmod.shape, dtype=torch.float32, device=h.device)
-
-    # ---------------- context stream tail (needed first: the joint attention backward wants d(cao))
+    K.update(h1=h1, u=u, t_ff=t_ff)
+    if not keep:
+        K.update(nh=nh, nh2=nh2, nc=nc, nh3=nh3, ffh=ffh)
+    h_out = T.rowcombine(t_ff, gate_a=sl(mod, 5), rows_per_gate_a=N, b=h1) if keep else None
+    c_out = None
     if not pre_only:
         t_catt = lin_fwd(cao, blk.attn.to_add_out)
         c1 = T.rowcombine(t_catt, gate_a=sl(cmod, 2), rows_per_gate_a=Lc, b=c)
@@ -202,11 +332,45 @@ def joint_block_backward(blk: JointTransformerBlock, h: torch.Tensor, c: torch.T
         cu = lin_fwd(nc3, c1f)
         cffh = T.act_fwd(cu, ACT_GELU_TANH)
         t_cff = lin_fwd(cffh, c2f)
+        K.update(t_catt=t_catt, c1=c1, cu=cu, t_cff=t_cff)
+        if keep:
+            c_out = T.rowcombine(t_cff, gate_a=sl(cmod, 5), rows_per_gate_a=Lc, b=c1)
+        else:
+            K.update(nc3=nc3, cffh=cffh)
+    return h_out, c_out, K
+
+
+def joint_block_backward_kept(blk: JointTransformerBlock, K: Dict[str, Optional[torch.Tensor]], n_img: int, dh: torch.Tensor,
+                              dc: Optional[torch.Tensor], G: Grads):
+    """Backward of the block from the kept set of joint_block_forward_train; dh / dc: gradients of the block outputs.  A LayerNorm
+    or activation output the set does not hold is re-derived right before the weight gradient that reads it (not at all when
+    that weight is frozen).  Returns (dh_in, dc_in, dst)."""
+    D = blk.dim
+    h, c, st, mod, cmod = K["h"], K["c"], K["st"], K["mod"], K["cmod"]
+    N, Lc = h.shape[0] // n_img, c.shape[0] // n_img
+    dual, pre_only = blk.use_dual_attention, blk.context_pre_only
+    sl = lambda m, i: m[:, i * D:(i + 1) * D]
+    id_map = ops.rowmap_identity(n_img, N)
+    cs, cb = (0, 1) if pre_only else (1, 0)
+    qkv, rinv, cqkv, crinv, ao, cao, lse = K["qkv"], K["rinv"], K["cqkv"], K["crinv"], K["ao"], K["cao"], K["lse"]
+    t_att, h1, u, t_ff = K["t_att"], K["h1"], K["u"], K["t_ff"]
+    f1, f2 = blk.ff.net[0].proj, blk.ff.net[2]
+    wants = lambda lin: lin.weight.requires_grad
+
+    dmod = torch.zeros(mod.shape, dtype=torch.float32, device=h.device)
+    dcmod = torch.zeros(cmod.shape, dtype=torch.float32, device=h.device)
+
+    # ---------------- context stream tail (needed first: the joint attention backward wants d(cao))
+    if not pre_only:
+        t_catt, c1, cu, t_cff = K["t_catt"], K["c1"], K["cu"], K["t_cff"]
+        c1f, c2f = blk.ff_context.net[0].proj, blk.ff_context.net[2]
         # c2 = c1 + gate_mlp * t_cff
         T.segsum(t_cff, dc, rows_per_group=Lc, out=sl(dcmod, 5))
         dct = T.rowcombine(dc, gate_a=sl(cmod, 5), rows_per_gate_a=Lc)
-        dcffh = lin_bwd(G, c2f, cffh, dct)
-        dcu = T.act_bwd(cu, dcffh, ACT_GELU_TANH)
+        dcu = _act_lin_bwd(G, c2f, cu, K.get("cffh"), dct, ACT_GELU_TANH)
+        nc3 = K.get("nc3")
+        if nc3 is None and wants(c1f):
+            nc3 = ops.layernorm(c1, eps=1e-6, scale=sl(cmod, 4), shift=sl(cmod, 3), rows_per_mod=Lc)
         dnc3 = lin_bwd(G, c1f, nc3, dcu)
         dc1 = dc.clone()
         T.layernorm_bwd(c1, dnc3, eps=1e-6, dx=dc1, accumulate=True, scale=sl(cmod, 4), rows_per_mod=Lc,
@@ -222,14 +386,23 @@ def joint_block_backward(blk: JointTransformerBlock, h: torch.Tensor, c: torch.T
     # ---------------- sample stream: h2 = h1 + gate_mlp * t_ff
     T.segsum(t_ff, dh, rows_per_group=N, out=sl(dmod, 5))
     dt = T.rowcombine(dh, gate_a=sl(mod, 5), rows_per_gate_a=N)
-    dffh = lin_bwd(G, f2, ffh, dt)
-    du = T.act_bwd(u, dffh, ACT_GELU_TANH)
+    du = _act_lin_bwd(G, f2, u, K.get("ffh"), dt, ACT_GELU_TANH)
+    nh3 = K.get("nh3")
+    if nh3 is None and wants(f1):
+        nh3 = ops.layernorm(h1, eps=1e-6, scale=sl(mod, 4), shift=sl(mod, 3), rows_per_mod=N)
     dnh3 = lin_bwd(G, f1, nh3, du)
+    del nh3
     dh1 = dh.clone()
     T.layernorm_bwd(h1, dnh3, eps=1e-6, dx=dh1, accumulate=True, scale=sl(mod, 4), rows_per_mod=N,
                     dgamma=sl(dmod, 4), dbeta=sl(dmod, 3), grad_per_group=True)
+    nh, nh2 = K.get("nh"), K.get("nh2")
+    if nh is None and (wants(blk.attn.to_q) or (dual and wants(blk.attn2.to_q))):
+        nh2 = torch.empty_like(h) if dual else None
+        nh = ops.layernorm(h, eps=1e-6, scale=sl(mod, 1), shift=sl(mod, 0), rows_per_mod=N,
+                           scale2=sl(mod, 7) if dual else None, shift2=sl(mod, 6) if dual else None, out2=nh2)
     dnh2 = None
     if dual:       # h1 = h1a + gate2 * t_att2
+        qkv2, rinv2, ao2, lse2, t_att2 = K["qkv2"], K["rinv2"], K["ao2"], K["lse2"], K["t_att2"]
         T.segsum(t_att2, dh1, rows_per_group=N, out=sl(dmod, 8))
         dt2 = T.rowcombine(dh1, gate_a=sl(mod, 8), rows_per_gate_a=N)
         dao2 = lin_bwd(G, blk.attn2.to_out[0], ao2, dt2)
@@ -251,6 +424,9 @@ def joint_block_backward(blk: JointTransformerBlock, h: torch.Tensor, c: torch.T
     qk_norm_bwd(G, blk.attn, qkv, rinv, dqkv)
     qk_norm_bwd(G, blk.attn, cqkv, crinv, dcqkv, added=True)
     dnh = qkv_bwd(G, blk.attn, nh, dqkv)
+    nc = K.get("nc")
+    if nc is None and wants(blk.attn.add_q_proj):
+        nc = ops.layernorm(c, eps=1e-6, scale=sl(cmod, cs), shift=sl(cmod, cb), rows_per_mod=Lc)
     dnc = qkv_bwd(G, blk.attn, nc, dcqkv, added=True)
 
     # ---------------- the two AdaLN layers at the block input
@@ -267,45 +443,68 @@ def joint_block_backward(blk: JointTransformerBlock, h: torch.Tensor, c: torch.T
     return dh1, dc1, dst
 
 
+def joint_block_backward(blk: JointTransformerBlock, h: torch.Tensor, c: torch.Tensor, st: torch.Tensor, n_img: int,
+                         dh: torch.Tensor, dc: Optional[torch.Tensor], G: Grads):
+    """Recompute + backward of JointTransformerBlock.run: the training forward from the block INPUTS, then the backward from
+    its kept set.  dh / dc: gradients of the block outputs.  Returns (dh_in, dc_in, dst)."""
+    _, _, K = joint_block_forward_train(blk, h, c, st, n_img, keep=False)
+    return joint_block_backward_kept(blk, K, n_img, dh, dc, G)
+
+
+def _save_kept(ctx, K: Dict[str, Optional[torch.Tensor]]) -> None:
+    ctx.kept_names = list(K)
+    ctx.save_for_backward(*K.values())
+
+
+def _load_kept(ctx) -> Dict[str, Optional[torch.Tensor]]:
+    return dict(zip(ctx.kept_names, ctx.saved_tensors))
+
+
 @ops.carries_gemm_scope
 class JointBlockFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, blk, n_img, h, c, st, *params):
-        ctx.blk, ctx.n_img = blk, n_img
-        ctx.save_for_backward(h, c, st)
+    def forward(ctx, blk, n_img, keep, h, c, st, *params):
+        ctx.blk, ctx.n_img, ctx.keep = blk, n_img, keep
         ctx.np = len(params)
         with torch.no_grad():
-            c_out, h_out = blk.run(h.clone(), c.clone(), st, n_img)
+            if keep:
+                h_out, c_out, K = joint_block_forward_train(blk, h, c, st, n_img, keep=True)
+                _save_kept(ctx, K)
+            else:
+                ctx.save_for_backward(h, c, st)
+                c_out, h_out = blk.run(h.clone(), c.clone(), st, n_img)
         if c_out is None:
             c_out = c.new_zeros(())           # context_pre_only: the context stream ends here
         return h_out, c_out
 
     @staticmethod
     def backward(ctx, dh, dc):
-        h, c, st = ctx.saved_tensors
         blk = ctx.blk
         G = Grads()
-        if blk.context_pre_only:
-            dc = None
-        dh_in, dc_in, dst = joint_block_backward(blk, h, c, st, ctx.n_img, dh.contiguous(),
-                                                 None if dc is None else dc.contiguous(), G)
+        dc = None if blk.context_pre_only else dc.contiguous()
+        if ctx.keep:
+            dh_in, dc_in, dst = joint_block_backward_kept(blk, _load_kept(ctx), ctx.n_img, dh.contiguous(), dc, G)
+        else:
+            h, c, st = ctx.saved_tensors
+            dh_in, dc_in, dst = joint_block_backward(blk, h, c, st, ctx.n_img, dh.contiguous(), dc, G)
         ps = _params(blk)
-        return (None, None, dh_in, dc_in, dst) + _grads_for(G, ps, ctx.needs_input_grad[5:])
+        return (None, None, None, dh_in, dc_in, dst) + _grads_for(G, ps, ctx.needs_input_grad[6:])
 
 
-def joint_block_train(blk: JointTransformerBlock, h, c, st, n_img: int):
-    return JointBlockFn.apply(blk, n_img, h, c, st, *_params(blk))
+def joint_block_train(blk: JointTransformerBlock, h, c, st, n_img: int, keep: bool = False):
+    """keep: the block keeps its activations instead of recomputing them in backward (ignored without autograd: nothing is kept)"""
+    return JointBlockFn.apply(blk, n_img, bool(keep) and torch.is_grad_enabled(), h, c, st, *_params(blk))
 
 
 # ------------------------------------------------------------------------------------------ VT block + mixer
-def vt_block_backward(blk: VTSelfAttentionBlock, h: torch.Tensor, emb: torch.Tensor, rows_per_emb: int, rowmap,
-                      group_mask, dense_mask, alpha: torch.Tensor, rows_per_alpha: int, dy: torch.Tensor, G: Grads):
-    """Recompute + backward of VTSelfAttentionBlock.run followed by the AlphaBlender
-    (crossview_temporal.py:562-582, 68-72; crossview_temporal_dit.py:320-327,363-370).
-    Returns (dh, demb fp32 [G, D], dalpha fp32 [B])."""
+def vt_block_forward_train(blk: VTSelfAttentionBlock, h: torch.Tensor, emb: torch.Tensor, rows_per_emb: int, rowmap,
+                           group_mask, dense_mask, alpha: torch.Tensor, rows_per_alpha: int, keep: bool = False):
+    """Training forward of VTSelfAttentionBlock.run followed by the AlphaBlender (crossview_temporal.py:562-582, 68-72;
+    crossview_temporal_dit.py:320-327,363-370).  Returns (blended, kept).  keep=False: every intermediate is in kept and the blend
+    is not formed; keep=True: blended = alpha * h + (1 - alpha) * out is, and kept holds what kept_bytes counts - `out` from before
+    the blend among it, for d(alpha)."""
     D = blk.dim
     ln = lambda x, n, **kw: ops.layernorm(x, eps=1e-5, weight=_bf(n.weight), bias=_bf(n.bias), **kw)
-    # ---------------- recompute
     xs0 = torch.empty_like(h)
     y = ln(h, blk.norm_in, addvec=emb, rows_per_add=rows_per_emb, xsum=xs0)          # xs0 = h + emb
     pi, l2i = blk.ff_in.net[0].proj, blk.ff_in.net[2]
@@ -318,21 +517,40 @@ def vt_block_backward(blk: VTSelfAttentionBlock, h: torch.Tensor, emb: torch.Ten
     lse = torch.empty(rowmap.n_problems * blk.heads * rowmap.L0, dtype=torch.float32, device=h.device)
     ops.attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], ao, rowmap, blk.heads, group_mask=group_mask,
                   dense_mask=dense_mask, lse=lse)
-    to_out = blk.attn1.to_out[0]
-    xs2 = lin_fwd(ao, to_out, epilogue=ops.EPI_RESID, res=xs1)
+    xs2 = lin_fwd(ao, blk.attn1.to_out[0], epilogue=ops.EPI_RESID, res=xs1)
     y3 = ln(xs2, blk.norm3)
     p3, l23 = blk.ff.net[0].proj, blk.ff.net[2]
     u3 = lin_fwd(y3, p3)
     g3 = T.geglu_fwd(u3)
     out = lin_fwd(g3, l23, epilogue=ops.EPI_RESID, res=xs2)
+    K = dict(h=h, emb=emb, alpha=alpha, u1=u1, xs1=xs1, qkv=qkv, rinv=rinv, ao=ao, lse=lse, xs2=xs2, u3=u3, out=out)
+    if not keep:
+        K.update(y=y, g1=g1, y1=y1, y3=y3, g3=g3)
+        return None, K
+    one_minus = (1.0 - alpha).contiguous()
+    blended = T.rowcombine(h, coef_a=alpha, rows_per_coef_a=rows_per_alpha, b=out, coef_b=one_minus, rows_per_coef_b=rows_per_alpha)
+    return blended, K
+
+
+def vt_block_backward_kept(blk: VTSelfAttentionBlock, K: Dict[str, Optional[torch.Tensor]], rows_per_emb: int, rowmap,
+                           group_mask, dense_mask, rows_per_alpha: int, dy: torch.Tensor, G: Grads):
+    """Backward of the VT block and its mixer from the kept set of vt_block_forward_train (a LayerNorm or GEGLU output it does
+    not hold is re-derived, as in joint_block_backward_kept).  Returns (dh, demb fp32 [G, D], dalpha fp32 [B])."""
+    D = blk.dim
+    ln = lambda x, n, **kw: ops.layernorm(x, eps=1e-5, weight=_bf(n.weight), bias=_bf(n.bias), **kw)
+    h, emb, alpha = K["h"], K["emb"], K["alpha"]
+    u1, xs1, qkv, rinv, ao, lse, xs2, u3 = K["u1"], K["xs1"], K["qkv"], K["rinv"], K["ao"], K["lse"], K["xs2"], K["u3"]
+    pi, l2i = blk.ff_in.net[0].proj, blk.ff_in.net[2]
+    p3, l23 = blk.ff.net[0].proj, blk.ff.net[2]
+    to_out = blk.attn1.to_out[0]
+    wants = lambda lin: lin.weight.requires_grad
 
     # ---------------- mixer: blended = alpha * h + (1 - alpha) * out
     one_minus = (1.0 - alpha).contiguous()
     # d(alpha) = <dy, h - out>: one pass, fp32 difference before the product, fp32 column sums, summed in fp64 - the value
     # is a heavily cancelling sum (sum|terms| / |sum| = 200-3000 on the test configurations), so no partial sum is rounded
-    dalpha = T.segsum_diff(dy, h, out, rows_per_group=rows_per_alpha).double().sum(-1).float()
+    dalpha = T.segsum_diff(dy, h, K.pop("out"), rows_per_group=rows_per_alpha).double().sum(-1).float()
     dout = T.rowcombine(dy, coef_a=one_minus, rows_per_coef_a=rows_per_alpha)
-    del out
 
     def ln_bwd(x, n, dyy, dx, **kw):
         dg = torch.zeros(1, D, dtype=torch.float32, device=h.device)
@@ -343,9 +561,12 @@ def vt_block_backward(blk: VTSelfAttentionBlock, h: torch.Tensor, emb: torch.Ten
 
     # out = xs2 + ff(norm3(xs2))
     dxs2 = dout
-    dg3 = lin_bwd(G, l23, g3, dout)
-    du3 = T.geglu_bwd(u3, dg3)
+    du3 = _act_lin_bwd(G, l23, u3, K.get("g3"), dout, None)
+    y3 = K.get("y3")
+    if y3 is None and wants(p3):
+        y3 = ln(xs2, blk.norm3)
     dy3 = lin_bwd(G, p3, y3, du3)
+    del y3
     ln_bwd(xs2, blk.norm3, dy3, dxs2)
     # xs2 = xs1 + to_out(attn(norm1(xs1)))
     dao = lin_bwd(G, to_out, ao, dxs2)
@@ -353,13 +574,20 @@ def vt_block_backward(blk: VTSelfAttentionBlock, h: torch.Tensor, emb: torch.Ten
     ops.attention_bwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], ao, dao, dqkv[:, :D], dqkv[:, D:2 * D], dqkv[:, 2 * D:],
                       rowmap, blk.heads, lse, group_mask=group_mask, dense_mask=dense_mask)
     qk_norm_bwd(G, blk.attn1, qkv, rinv, dqkv)
+    y1 = K.get("y1")
+    if y1 is None and wants(blk.attn1.to_q):
+        y1 = ln(xs1, blk.norm1)
     dy1 = qkv_bwd(G, blk.attn1, y1, dqkv)
+    del y1
     dxs1 = dxs2
     ln_bwd(xs1, blk.norm1, dy1, dxs1)
     # xs1 = xs0 + ff_in(norm_in(xs0))
-    dg1 = lin_bwd(G, l2i, g1, dxs1)
-    du1 = T.geglu_bwd(u1, dg1)
+    du1 = _act_lin_bwd(G, l2i, u1, K.get("g1"), dxs1, None)
+    y = K.get("y")
+    if y is None and wants(pi):
+        y = ln(h, blk.norm_in, addvec=emb, rows_per_add=rows_per_emb)
     dyin = lin_bwd(G, pi, y, du1)
+    del y
     dxs0 = dxs1
     ln_bwd(h, blk.norm_in, dyin, dxs0, addvec=emb, rows_per_add=rows_per_emb)
     # xs0 = h + emb[row // rows_per_emb]   (one embedding row per token - explicit perspective modelling - needs no sum)
@@ -368,34 +596,54 @@ def vt_block_backward(blk: VTSelfAttentionBlock, h: torch.Tensor, emb: torch.Ten
     return dh, demb, dalpha
 
 
+def vt_block_backward(blk: VTSelfAttentionBlock, h: torch.Tensor, emb: torch.Tensor, rows_per_emb: int, rowmap,
+                      group_mask, dense_mask, alpha: torch.Tensor, rows_per_alpha: int, dy: torch.Tensor, G: Grads):
+    """Recompute + backward of VTSelfAttentionBlock.run followed by the AlphaBlender: the training forward from the block
+    INPUTS, then the backward from its kept set.  Returns (dh, demb fp32 [G, D], dalpha fp32 [B])."""
+    _, K = vt_block_forward_train(blk, h, emb, rows_per_emb, rowmap, group_mask, dense_mask, alpha, rows_per_alpha, keep=False)
+    return vt_block_backward_kept(blk, K, rows_per_emb, rowmap, group_mask, dense_mask, rows_per_alpha, dy, G)
+
+
 @ops.carries_gemm_scope
 class VTBlockFn(torch.autograd.Function):
     """h_out = AlphaBlender(h, VTSelfAttentionBlock(h + emb)); inputs that carry gradients: h, emb, alpha."""
 
     @staticmethod
-    def forward(ctx, blk, rowmap, rows_per_emb, rows_per_alpha, group_mask, dense_mask, h, emb, alpha, *params):
+    def forward(ctx, blk, rowmap, rows_per_emb, rows_per_alpha, group_mask, dense_mask, keep, h, emb, alpha, *params):
         ctx.blk, ctx.rowmap, ctx.rpe, ctx.rpa = blk, rowmap, rows_per_emb, rows_per_alpha
-        ctx.gm, ctx.dm = group_mask, dense_mask
-        ctx.save_for_backward(h, emb, alpha)
+        ctx.gm, ctx.dm, ctx.keep = group_mask, dense_mask, keep
         with torch.no_grad():
-            out = h.clone()
-            blk.run(out, rowmap, emb=emb, rows_per_emb=rows_per_emb, group_mask=group_mask, dense_mask=dense_mask,
-                    blend_alpha=alpha, rows_per_alpha=rows_per_alpha, blend_into=out)
+            if keep:
+                out, K = vt_block_forward_train(blk, h, emb, rows_per_emb, rowmap, group_mask, dense_mask, alpha, rows_per_alpha,
+                                                keep=True)
+                _save_kept(ctx, K)
+            else:
+                ctx.save_for_backward(h, emb, alpha)
+                out = h.clone()
+                blk.run(out, rowmap, emb=emb, rows_per_emb=rows_per_emb, group_mask=group_mask, dense_mask=dense_mask,
+                        blend_alpha=alpha, rows_per_alpha=rows_per_alpha, blend_into=out)
         return out
 
     @staticmethod
     def backward(ctx, dy):
-        h, emb, alpha = ctx.saved_tensors
         G = Grads()
-        dh, demb, dalpha = vt_block_backward(ctx.blk, h, emb, ctx.rpe, ctx.rowmap, ctx.gm, ctx.dm, alpha, ctx.rpa,
-                                             dy.contiguous(), G)
+        if ctx.keep:
+            K = _load_kept(ctx)
+            emb, alpha = K["emb"], K["alpha"]
+            dh, demb, dalpha = vt_block_backward_kept(ctx.blk, K, ctx.rpe, ctx.rowmap, ctx.gm, ctx.dm, ctx.rpa, dy.contiguous(), G)
+        else:
+            h, emb, alpha = ctx.saved_tensors
+            dh, demb, dalpha = vt_block_backward(ctx.blk, h, emb, ctx.rpe, ctx.rowmap, ctx.gm, ctx.dm, alpha, ctx.rpa,
+                                                 dy.contiguous(), G)
         ps = _params(ctx.blk)
-        return (None, None, None, None, None, None, dh, demb.to(emb.dtype), dalpha.to(alpha.dtype)) + \
-            _grads_for(G, ps, ctx.needs_input_grad[9:])
+        return (None, None, None, None, None, None, None, dh, demb.to(emb.dtype), dalpha.to(alpha.dtype)) + \
+            _grads_for(G, ps, ctx.needs_input_grad[10:])
 
 
-def vt_block_train(blk, h, rowmap, emb, rows_per_emb, alpha, rows_per_alpha, group_mask=None, dense_mask=None):
-    return VTBlockFn.apply(blk, rowmap, rows_per_emb, rows_per_alpha, group_mask, dense_mask, h, emb, alpha, *_params(blk))
+def vt_block_train(blk, h, rowmap, emb, rows_per_emb, alpha, rows_per_alpha, group_mask=None, dense_mask=None, keep: bool = False):
+    """keep: the block keeps its activations instead of recomputing them in backward (ignored without autograd)"""
+    return VTBlockFn.apply(blk, rowmap, rows_per_emb, rows_per_alpha, group_mask, dense_mask, bool(keep) and torch.is_grad_enabled(),
+                           h, emb, alpha, *_params(blk))
 
 
 def alpha_train(mixer: AlphaBlender, image_only_indicator: Optional[torch.Tensor], batch: int) -> torch.Tensor:
@@ -773,6 +1021,10 @@ def forward_train(model, sample, timestep, encoder_hidden_states, pooled_project
     if model.enable_temporal and disable_temporal is None:
         disable_temporal = torch.zeros(B, dtype=torch.bool, device=dev)
 
+    wants = resolve_activation_policy(getattr(model, "activation_policy", "recompute"), model.gradient_checkpointing,
+                                      model.temporal_gradient_checkpointing, model.crossview_gradient_checkpointing)
+    plan = ActivationPlan(getattr(model, "activation_budget_gib", None))
+
     residuals: List[torch.Tensor] = []
     if model.condition_image_adapter is not None and condition_image_tensor is not None:            # :459-462
         ad = model.condition_image_adapter
@@ -784,7 +1036,8 @@ def forward_train(model, sample, timestep, encoder_hidden_states, pooled_project
     for i, block in enumerate(model.transformer_blocks):
         if residuals:
             h = AddFn.apply(h, residuals.pop(0))                                                   # :491-494
-        h, c = joint_block_train(block, h, c, st, I)
+        h, c = joint_block_train(block, h, c, st, I, keep=plan.decide(f"transformer_blocks.{i}", wants["joint"],
+                                                                       joint_kept_bytes(block, h, c, I)))
         if model.enable_temporal and i in model.temporal_block_layers:
             k = model.temporal_block_layers.index(i)
             idx = torch.arange(Tn, device=dev).view(1, Tn, 1).expand(B, Tn, V)
@@ -798,8 +1051,10 @@ def forward_train(model, sample, timestep, encoder_hidden_states, pooled_project
             mk = ops.rowmap_temporal_full if tt == "full" else \
                 ops.rowmap_temporal_rowwise if tt == "rowwise" else ops.rowmap_temporal_pointwise
             alpha = alpha_train(model.time_mixers[k], disable_temporal, B)
-            h = vt_block_train(model.temporal_transformer_blocks[k], h, mk(B, Tn, V, height, width), seq_emb, rpe,
-                               alpha, Tn * V * N)
+            tblk, rm = model.temporal_transformer_blocks[k], mk(B, Tn, V, height, width)
+            h = vt_block_train(tblk, h, rm, seq_emb, rpe, alpha, Tn * V * N,
+                               keep=plan.decide(f"temporal_transformer_blocks.{k}", wants["temporal"],
+                                                vt_kept_bytes(tblk, h, rm, seq_emb, alpha)))
         if model.enable_crossview and i in model.crossview_block_layers:
             k = model.crossview_block_layers.index(i)
             idx = torch.arange(V, device=dev).view(1, 1, V).expand(B, Tn, V)
@@ -816,9 +1071,12 @@ def forward_train(model, sample, timestep, encoder_hidden_states, pooled_project
             else:
                 raise NotImplementedError(f"Not support {ct}")
             alpha = alpha_train(model.view_mixers[k], disable_crossview, B)
-            h = vt_block_train(model.crossview_transformer_blocks[k], h, rm, vemb, rpe, alpha, Tn * V * N,
-                               group_mask=gmask, dense_mask=dmask)
+            cblk = model.crossview_transformer_blocks[k]
+            h = vt_block_train(cblk, h, rm, vemb, rpe, alpha, Tn * V * N, group_mask=gmask, dense_mask=dmask,
+                               keep=plan.decide(f"crossview_transformer_blocks.{k}", wants["crossview"],
+                                                vt_kept_bytes(cblk, h, rm, vemb, alpha)))
 
+    model.activation_plan = plan
     geom = (I, model.out_channels, height, width, p, N, D)
     out = OutFn.apply(model, geom, h, st, *(_params(model.norm_out) + _params(model.proj_out)))
     return out.view(B, Tn, V, model.out_channels, height * p, width * p)

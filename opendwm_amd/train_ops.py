@@ -86,6 +86,32 @@ def geglu_bwd(u: torch.Tensor, dg: torch.Tensor) -> torch.Tensor:
     return du
 
 
+def act_bwd_recompute(x: torch.Tensor, dy: torch.Tensor, act: int, y_out: Optional[torch.Tensor] = None,
+                      dx: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(act(x), dy * act'(x)) from one read of x: act_fwd and act_bwd in one launch, bit-equal to both"""
+    y_out = torch.empty_like(x) if y_out is None else y_out
+    dx = torch.empty_like(x) if dx is None else dx
+    if dy.numel() != x.numel() or y_out.numel() != x.numel() or dx.numel() != x.numel():
+        raise RuntimeError("act_bwd_recompute: x, dy, y_out and dx must have one element count")
+    _call("dwm_act_bwd_recompute", _p(x), _p(dy), _p(y_out), _p(dx), x.numel(), act)
+    return y_out, dx
+
+
+def geglu_bwd_recompute(u: torch.Tensor, dg: torch.Tensor, g_out: Optional[torch.Tensor] = None,
+                        du: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(geglu_fwd(u), geglu_bwd(u, dg)) from one read of u"""
+    _chk2d(u, "u"); _chk2d(dg, "dg")
+    rows, two = u.shape
+    g_out = torch.empty((rows, two // 2), dtype=bf16, device=u.device) if g_out is None else g_out
+    du = torch.empty_like(u) if du is None else du
+    _chk2d(g_out, "g_out"); _chk2d(du, "du")
+    if dg.shape != (rows, two // 2) or g_out.shape != dg.shape or du.shape != u.shape:
+        raise RuntimeError("geglu_bwd_recompute: u and du [rows, 2 * inner], dg and g_out [rows, inner] expected")
+    _call("dwm_geglu_bwd_recompute", _p(u), u.stride(0), _p(dg), dg.stride(0), rows, two // 2, _p(g_out), g_out.stride(0),
+          _p(du), du.stride(0))
+    return g_out, du
+
+
 def rowcombine(a: torch.Tensor, *, gate_a: Optional[torch.Tensor] = None, rows_per_gate_a: int = 1,
                coef_a: Optional[torch.Tensor] = None, rows_per_coef_a: int = 1,
                b: Optional[torch.Tensor] = None, coef_b: Optional[torch.Tensor] = None, rows_per_coef_b: int = 1,
