@@ -667,6 +667,27 @@ int dwm_block_permute(const dwm_block_permute_args* args, void* stream);
 int dwm_head_exchange(const void* src, void* dst, int64_t rows, int32_t S, int32_t R, int64_t Dr, int32_t elem_size, int64_t ld,
                       int32_t dir, void* stream);
 
+/* FIFO slide: ONE launch moves a LIST of dense buffers [outer][T][inner_bytes] by one frame along T, in place:
+ *   buf[o][t] = buf[o][t + 1] for t < T - 1,   buf[o][T - 1] = fresh[o % fresh_outer]      (T == 1: the copy of fresh)
+ * fresh: [fresh_outer][inner_bytes] with fresh_outer a divisor of outer (the two CFG halves of a model input take one noise frame).
+ * convert = 0: fresh holds the buffer's bytes.  convert = 1: the buffer is bf16 and fresh is fp32 ([fresh_outer][inner_bytes / 2] floats),
+ * rounded to nearest even exactly as dwm_cast_f32_to_bf16 does.  inner_bytes: a positive multiple of 2.  Rows are moved in pieces of
+ * W bytes, W = 16 if inner_bytes and both pointers are multiples of 16, else 4 if they are multiples of 4, else 2 (buf 2-byte aligned,
+ * fresh 2-byte, with convert 4-byte aligned: else DWM_EALIGN); n = outer * inner_bytes / W is the item's column count and what the
+ * tables cut: block b owns columns [block_start[b], min(block_start[b] + chunk, n)) of item block_item[b], ceil(n / chunk) blocks per
+ * item as for dwm_adamw_multi; chunk a multiple of 256, at most 2^20.  Every column is walked by one thread, so the result is
+ * deterministic, and no byte outside [buf, buf + outer * T * inner_bytes) is written.
+ * `items` / block_item / block_start are DEVICE arrays (built once for buffers that stay where they are); `host_items` is the HOST
+ * copy of the same n_items structs, read by the argument checks of every call - nothing is launched on a refusal:
+ *   DWM_EINVAL       null pointers, sizes <= 0, odd inner_bytes, outer % fresh_outer != 0, convert not 0 / 1, a wrong n, fresh overlapping
+ *                    buf, n_blocks != the blocks the items need
+ *   DWM_EUNSUPPORTED 2^31 or more columns, or 2^46 or more bytes, in one item */
+typedef struct dwm_fifo_item {
+    void* buf; const void* fresh; int64_t outer; int64_t T; int64_t inner_bytes; int64_t fresh_outer; int64_t convert; int64_t n;
+} dwm_fifo_item;
+int dwm_fifo_slide_multi(const dwm_fifo_item* host_items, int64_t n_items, const dwm_fifo_item* items, const int32_t* block_item,
+                         const int64_t* block_start, int64_t n_blocks, int64_t chunk, void* stream);
+
 /* y fp32 [rows, ldy] (+)= x bf16 [rows, ldx] */
 int dwm_cast_bf16_to_f32(const void* x, int64_t ldx, float* y, int64_t ldy, int64_t rows, int64_t cols,
                          int32_t accumulate, void* stream);

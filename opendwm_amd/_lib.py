@@ -116,6 +116,11 @@ class AdamW8Item(C.Structure):          # one row of the device array train_ops.
     _fields_ = [("p", _vp), ("g", _vp), ("m_q", _vp), ("m_absmax", _vp), ("v_q", _vp), ("v_absmax", _vp), ("p_bf16", _vp), ("n", _i64)]
 
 
+class FifoItem(C.Structure):            # one entry of the list dwm_fifo_slide_multi slides (8 x 8 bytes; host array and device copy)
+    _fields_ = [("buf", _vp), ("fresh", _vp), ("outer", _i64), ("T", _i64), ("inner_bytes", _i64), ("fresh_outer", _i64),
+                ("convert", _i64), ("n", _i64)]
+
+
 class VaeAttnArgs(C.Structure):
     _fields_ = [("q", _vp), ("k", _vp), ("v", _vp), ("out", _vp), ("ldq", _i64), ("ldk", _i64), ("ldv", _i64), ("ldo", _i64),
                 ("I", _i64), ("P", _i64), ("C", _i32), ("scale", _f32)]
@@ -208,6 +213,7 @@ SIGNATURES = {
     "dwm_grad_scale_multi": (_i32, [_vp, _vp, _vp, _i64, _i64, _f32, _vp]),
     "dwm_block_permute": (_i32, [C.POINTER(BlockPermuteArgs), _vp]),
     "dwm_head_exchange": (_i32, [_vp, _vp, _i64, _i32, _i32, _i64, _i32, _i64, _i32, _vp]),
+    "dwm_fifo_slide_multi": (_i32, [C.POINTER(FifoItem), _i64, _vp, _vp, _vp, _i64, _i64, _vp]),
     "dwm_cast_bf16_to_f32": (_i32, [_vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp]),
     "dwm_groupnorm_bwd": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _f32, _vp, _vp, _i32, _i32, _vp, _vp, _vp,
                                  C.POINTER(RowMap2D), C.POINTER(GnImgMap), _vp]),

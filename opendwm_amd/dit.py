@@ -403,6 +403,77 @@ class DiTCrossviewTemporalConditionModel(_Base):
         flag = image_only_indicator.reshape(1, batch).to(device=sig.device, dtype=torch.bool)
         return list(torch.where(flag, torch.ones((), device=sig.device), sig).contiguous())
 
+    # ---- cached layout residuals (the adapter is per image: a cache of [2B, T, V] images can be advanced frame by frame)
+    @staticmethod
+    def _adapter_cache_key(condition_image_tensor: torch.Tensor):
+        # the key holds the optimizer step (residuals of old adapter weights must not survive a training step) and
+        # the cache keeps the tensor alive (a freed tensor's address can be handed to the next same-shape batch)
+        from .blocks import STORE
+        return (condition_image_tensor.data_ptr(), condition_image_tensor._version, tuple(condition_image_tensor.shape), STORE.step)
+
+    def _cached_adapter_features(self, images: torch.Tensor, cd) -> list:
+        """the residuals the cache holds for `images` [..., C, H, W]: per level fp32 [I * N, D], I = the leading dimensions.  `cd`: the
+        store precision to return to (the forward's compute dtype)"""
+        from .blocks import STORE
+        # Computed once per condition tensor, so it can afford the fp32 accuracy path (dwm_gemm_f32, 3 x the MFMA work of
+        # the bf16 adapter, ~1 % of a 40-step loop): the adapter's error is the SAME at every denoise step and differs
+        # between the conditional and the unconditional half (different layout images), so classifier-free guidance
+        # multiplies it (4 c - 3 u) and the steps add it up coherently - it is what holds the text+layout model at
+        # 1.3e-2 after 40 steps when the text-only model is at 6e-3 (profiles/r4b_gpu_parity.log).
+        if self.adapter_cache_dtype == torch.float32:
+            STORE.set_precision(torch.float32)
+            try:
+                return self.condition_image_adapter.run(images)
+            finally:
+                STORE.set_precision(cd)
+        return self.condition_image_adapter.run(images, precise=True)
+
+    def adapter_cache_of(self, condition_image_tensor: torch.Tensor):
+        """the cached residuals (per level fp32 [2B * T * V * N, D]) if the cache holds them for this very tensor as it is now, else None"""
+        c = self._adapter_cache
+        if c[0] is None or c[2] is not condition_image_tensor or c[0] != self._adapter_cache_key(condition_image_tensor):
+            return None
+        return c[1]
+
+    def install_adapter_cache(self, condition_image_tensor: torch.Tensor, feats: list) -> None:
+        """Make `feats` (per level fp32 [2B * T * V * N, D], computed by this model at its current weights for the images
+        `condition_image_tensor` holds now) the cached residuals of that tensor.  The cache has ONE slot: a forward with another
+        condition tensor takes it over and drops its reference to the residuals it held.  Whoever keeps ADDRESSES of cached
+        residuals across forwards - a stream session: its captured graph and its slide tables - therefore holds the list itself
+        and puts it back before its next forward."""
+        self._adapter_cache = (self._adapter_cache_key(condition_image_tensor), feats, condition_image_tensor)
+
+    @torch.no_grad()
+    def advance_adapter_cache(self, frame_images: torch.Tensor, out=None) -> list:
+        """The residuals of ONE new frame, frame_images [2B, 1, V, C, H, W] in the dtype the condition tensor has, in the precision
+        the cache was built in (adapter_cache_dtype): per level [2B * V * N, D] fp32, written into the tensors of `out` if given -
+        the `fresh` operands of the FIFO slide (ops.FifoSlide) that moves the cached [2B, T, V * N * D] residuals of a streaming
+        session by one frame.  The adapter works image by image, so these are the rows a full recomputation over the slid condition
+        tensor would produce (up to the GEMM kernel chosen for the smaller row count)."""
+        with ops.gemm_4wave_scope(self.gemm_4wave):                    # as the forward that fills the cache
+            feats = self._cached_adapter_features(frame_images, bf16)  # (outside a forward the store precision is bf16)
+        if out is None:
+            return feats
+        for o, f in zip(out, feats):
+            o.copy_(f.view(o.shape))
+        return list(out)
+
+    @torch.no_grad()
+    def refill_adapter_cache(self, condition_image_tensor: torch.Tensor) -> bool:
+        """Recompute the cached residuals of `condition_image_tensor` INTO the tensors the cache already holds and take the tensor's
+        current state as the key: for a static condition buffer that was rewritten in place while a captured graph or a FifoSlide
+        plan holds the addresses of the cached residuals.  False (nothing done) if the cache holds nothing for this tensor or the
+        weights have changed since."""
+        c = self._adapter_cache
+        if c[0] is None or c[2] is not condition_image_tensor or c[0][2:] != self._adapter_cache_key(condition_image_tensor)[2:]:
+            return False
+        with ops.gemm_4wave_scope(self.gemm_4wave):
+            feats = self._cached_adapter_features(condition_image_tensor, bf16)
+        for o, f in zip(c[1], feats):
+            o.copy_(f)
+        self._adapter_cache = (self._adapter_cache_key(condition_image_tensor), c[1], condition_image_tensor)
+        return True
+
     @torch.no_grad()
     def _forward_infer(
         self,
@@ -517,23 +588,9 @@ class DiTCrossviewTemporalConditionModel(_Base):
         elif self.condition_image_adapter is not None and condition_image_tensor is not None:
             # the key holds the optimizer step (residuals of old adapter weights must not survive a training step) and
             # the cache keeps the tensor alive (a freed tensor's address can be handed to the next same-shape batch)
-            from .blocks import STORE
-            key = (condition_image_tensor.data_ptr(), condition_image_tensor._version, tuple(condition_image_tensor.shape), STORE.step)
+            key = self._adapter_cache_key(condition_image_tensor)
             if self._adapter_cache[0] != key:
-                # Computed once per condition tensor, so it can afford the fp32 accuracy path (dwm_gemm_f32, 3 x the MFMA work of
-                # the bf16 adapter, ~1 % of a 40-step loop): the adapter's error is the SAME at every denoise step and differs
-                # between the conditional and the unconditional half (different layout images), so classifier-free guidance
-                # multiplies it (4 c - 3 u) and the steps add it up coherently - it is what holds the text+layout model at
-                # 1.3e-2 after 40 steps when the text-only model is at 6e-3 (profiles/r4b_gpu_parity.log).
-                if self.adapter_cache_dtype == torch.float32:
-                    STORE.set_precision(torch.float32)
-                    try:
-                        feats = self.condition_image_adapter.run(condition_image_tensor)
-                    finally:
-                        STORE.set_precision(cd)
-                else:
-                    feats = self.condition_image_adapter.run(condition_image_tensor, precise=True)
-                self._adapter_cache = (key, feats, condition_image_tensor)
+                self._adapter_cache = (key, self._cached_adapter_features(condition_image_tensor, cd), condition_image_tensor)
             condition_residuals = list(self._adapter_cache[1])
             for f in condition_residuals:
                 if f.shape != h.shape:

@@ -273,10 +273,20 @@ class StreamingDriver:
     which every new frame costs inference_steps / T denoise steps and emits one frame.
 
     `frame_conditions`: embedded model kwargs of ONE frame ([2B, 1, V, ...]); entries named in
-    `autoregression_condition_exception_for_take_sequence` replace instead of queueing."""
+    `autoregression_condition_exception_for_take_sequence` replace instead of queueing.
+
+    persistent=True: the queue lives in the denoiser's stream session (CTSDDenoiser.begin_stream / advance_stream /
+    stream_window) instead of being re-built with torch.cat and re-prepared for every frame: static device buffers, one slide
+    launch per frame, the whole-step graph captured once, the layout adapter run on the new frame only.  Same calls, same host
+    random stream, same frames; `conditions` then names the session's buffers.  A second reset_streaming() of the same shapes
+    keeps buffers and graph."""
 
     def __init__(self, denoiser, inference_config: dict, decode: Optional[Callable] = None,
-                 generator: Optional[torch.Generator] = None, init_noise_sigma: float = 1.0):
+                 generator: Optional[torch.Generator] = None, init_noise_sigma: float = 1.0, persistent: bool = False):
+        self.persistent = bool(persistent)
+        if self.persistent and not all(hasattr(denoiser, m) for m in ("begin_stream", "advance_stream", "stream_window")):
+            raise ValueError(f"StreamingDriver(persistent=True) needs a denoiser with a stream session (begin_stream / advance_stream / "
+                             f"stream_window, as pipeline.CTSDDenoiser has); {type(denoiser).__name__} has none")
         self.denoiser, self.cfg = denoiser, dict(inference_config)
         self.decode = decode if decode is not None else (lambda lat, diffusion_forcing=False: lat.flatten(0, 2))
         self.generator, self.init_noise_sigma = generator, init_noise_sigma
@@ -318,6 +328,8 @@ class StreamingDriver:
         if self.latent_shape is None:
             raise RuntimeError("reset_streaming() first")
         steps, T, seq = self.cfg["inference_steps"], self.latent_shape[1], self.cfg["sequence_length_per_iteration"]
+        if self.persistent:
+            return self._send_persistent(frame_conditions, steps, T, seq)
         if frame_conditions is None:                                              # flush the queue
             if self.condition_count != seq:
                 raise RuntimeError("flush before the queue was filled")
@@ -336,6 +348,34 @@ class StreamingDriver:
             B = self.latent_shape[0]
             self.latents = torch.cat([self.latents[:, 1:], self._randn((B, 1) + self.latent_shape[2:])], 1)
             self.latents = self._window(steps - self.spi, steps)
+
+    def _send_persistent(self, frame_conditions: Optional[Dict], steps: int, T: int, seq: int):
+        """send_frame_condition on the denoiser's stream session: the same three phases, the same noise draws"""
+        den = self.denoiser
+
+        def window(start, stop, take_time=0):
+            self.frames.append(self.decode(den.stream_window(start, stop, take_time), diffusion_forcing=True))
+        if frame_conditions is None:                                              # flush the queue
+            if self.condition_count != seq:
+                raise RuntimeError("flush before the queue was filled")
+            for i in range(1, T):
+                window(steps + (i - 1) * self.spi, steps + i * self.spi, i)
+        elif self.condition_count < seq:                                          # gathering
+            self._queue(frame_conditions, slide=False)
+            self.condition_count += 1
+            if self.condition_count == seq:
+                if seq != T:
+                    raise ValueError(f"a persistent stream queues one condition frame per latent frame: sequence_length_per_iteration "
+                                     f"{seq} != {T} latent frames")
+                exc = self.cfg.get("autoregression_condition_exception_for_take_sequence", [])
+                den.begin_stream(self._randn(self.latent_shape), self.conditions, replace_keys=exc)
+                self.conditions = den.conditions                                  # the session's buffers from here on
+                window(0, steps)
+        else:                                                                     # steady state: one frame in, one out
+            B = self.latent_shape[0]
+            noise = torch.randn((B, 1) + self.latent_shape[2:], generator=self.generator) * self.init_noise_sigma
+            den.advance_stream(noise, frame_conditions)
+            window(steps - self.spi, steps)
 
     def send_frame(self, frame_batch: Optional[Dict], common_config: dict, embed_text: Optional[Callable] = None,
                    dtype=torch.bfloat16):

@@ -364,6 +364,73 @@ def head_exchange(src: torch.Tensor, dst: torch.Tensor, rows: int, S: int, R: in
     return dst
 
 
+FIFO_CHUNK = 1024               # columns (pieces of 16 / 4 / 2 bytes) per workgroup of dwm_fifo_slide_multi: 4 per thread, 16 KiB per frame
+
+
+class FifoSlide:
+    """A list of buffers that slide by one frame in ONE launch (dwm_fifo_slide_multi), planned once for buffers that stay where they are.
+
+    pairs: (buf, fresh, outer, T) per entry.  buf: a contiguous device tensor read as [outer][T][inner], updated in place:
+    buf[o][t] = buf[o][t + 1], buf[o][T - 1] = fresh[o % fresh_outer].  fresh: a contiguous device tensor of fresh_outer rows of the
+    same inner size (fresh_outer = its element count / the inner element count, a divisor of outer), of buf's dtype - or fp32 for a
+    bf16 buf, rounded as ops.cast_bf16 rounds.  It must not overlap buf.  The plan holds the tensors (their addresses are in its
+    device tables) and is valid as long as nobody reallocates them; `run()` launches on the current stream and can be captured."""
+
+    def __init__(self, pairs, chunk: int = FIFO_CHUNK):
+        pairs = list(pairs)
+        if not pairs:
+            raise RuntimeError("fifo_slide: an empty list")
+        self.chunk, self.tensors, rows = chunk, pairs, []
+        dev = pairs[0][0].device
+        for buf, fresh, outer, T in pairs:
+            if not (torch.is_tensor(buf) and torch.is_tensor(fresh) and buf.is_cuda and fresh.is_cuda):
+                raise RuntimeError("fifo_slide: expected device tensors (the HIP path has no CPU fallback)")
+            if buf.device != dev or fresh.device != dev or not buf.is_contiguous() or not fresh.is_contiguous():
+                raise RuntimeError("fifo_slide: contiguous tensors on one device expected")
+            convert = buf.dtype == bf16 and fresh.dtype == f32
+            if fresh.dtype != buf.dtype and not convert:
+                raise RuntimeError(f"fifo_slide: fresh is {fresh.dtype}, the buffer {buf.dtype} (only fp32 -> bf16 is converted)")
+            if outer <= 0 or T <= 0 or buf.numel() == 0 or buf.numel() % (outer * T) != 0:
+                raise RuntimeError(f"fifo_slide: a buffer of {buf.numel()} elements is not [outer = {outer}][T = {T}][inner]")
+            inner = buf.numel() // (outer * T)
+            inner_bytes = inner * buf.element_size()
+            if inner_bytes % 2 != 0:
+                raise RuntimeError(f"fifo_slide: rows of {inner_bytes} bytes (a multiple of 2 is needed)")
+            if fresh.numel() == 0 or fresh.numel() % inner != 0 or outer % (fresh.numel() // inner) != 0:
+                raise RuntimeError(f"fifo_slide: fresh has {fresh.numel()} elements: not a number of rows of {inner} that divides outer = {outer}")
+            b0, f0 = buf.data_ptr(), fresh.data_ptr()
+            if f0 < b0 + buf.numel() * buf.element_size() and b0 < f0 + fresh.numel() * fresh.element_size():
+                raise RuntimeError("fifo_slide: fresh overlaps the buffer it is shifted into")
+            a = b0 | f0 | inner_bytes
+            piece = 16 if a % 16 == 0 else 4 if a % 4 == 0 else 2          # fifo_piece_bytes of csrc/fifo.hip
+            rows.append((b0, f0, outer, T, inner_bytes, fresh.numel() // inner, int(convert), outer * (inner_bytes // piece)))
+        self.bytes_moved = sum((2 * r[3] - 1) * r[2] * r[4] for r in rows)        # read T - 1 frames + fresh, write T (fresh as buf bytes)
+        self.host_items = (_lib.FifoItem * len(rows))(*[_lib.FifoItem(*r) for r in rows])
+        self.items = torch.tensor(rows, dtype=torch.int64).to(dev)                   # [n, 8] = dwm_fifo_item[n]
+        bi, bs = [], []
+        for i, r in enumerate(rows):
+            nb = (r[-1] + chunk - 1) // chunk
+            bi.append(torch.full((nb,), i, dtype=torch.int32))
+            bs.append(torch.arange(nb, dtype=torch.int64) * chunk)
+        self.block_item, self.block_start = torch.cat(bi).to(dev), torch.cat(bs).to(dev)
+
+    def run(self) -> None:
+        _call("dwm_fifo_slide_multi", self.host_items, len(self.host_items), _p(self.items), _p(self.block_item), _p(self.block_start),
+              self.block_item.numel(), self.chunk)
+
+
+def fifo_slide(bufs: Sequence[torch.Tensor], freshes: Sequence[torch.Tensor]) -> None:
+    """slide every bufs[i] [outer, T, ...] by one frame along dim 1 in place and put freshes[i] ([fresh_outer, 1, ...] or
+    [fresh_outer, ...]) into its last frame: torch.cat([buf[:, 1:], fresh], 1) without the allocation, all buffers in one launch.
+    A one-off form of FifoSlide (which see); callers that slide the same buffers again and again keep a FifoSlide."""
+    if len(bufs) != len(freshes):
+        raise RuntimeError("fifo_slide: one fresh tensor per buffer")
+    for b in bufs:
+        if not torch.is_tensor(b) or b.dim() < 2:
+            raise RuntimeError("fifo_slide: buffers are tensors [outer, T, ...]")
+    FifoSlide([(b, f, b.shape[0], b.shape[1]) for b, f in zip(bufs, freshes)]).run()
+
+
 ATTN_Q_PRESCALED = 1 << 15     # dwm_attn_args.variant: q arrives with scale * log2(e) folded in by its producer
 ATTN_STREAM = 1 << 12           # ... the one-wave-per-SIMD streaming form of the resident kernel (attention_stream.hip): the library's default where it covers the launch
 ATTN_RES12 = 1 << 13            # ... keep the 12-wave resident kernel there (A/B measurements)

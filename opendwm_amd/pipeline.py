@@ -85,12 +85,16 @@ class CTSDDenoiser:
         self.use_graph = False
         self._graph = None
         self._side = None
+        self.graph_captures = 0          # whole-step graphs captured so far (a stream session captures one and keeps it)
+        self.slide_launches = 0          # dwm_fifo_slide_multi launches of the stream sessions so far
+        self._session = None
 
     def prepare(self, latents: torch.Tensor, conditions: Dict[str, torch.Tensor],
                 image_latents: Optional[torch.Tensor] = None, reference_frame_count: int = 0,
                 diffusion_forcing: bool = False, take_time: int = 0, clear_reference_frame_count: int = 0):
         dev = latents.device
         self._graph = None                                             # buffers below are re-created: capture again
+        self._session = None                                           # ... and a stream session has lost its buffers
         self.diffusion_forcing = diffusion_forcing
         self.take_time = take_time
         if diffusion_forcing and image_latents is not None:
@@ -225,6 +229,7 @@ class CTSDDenoiser:
             self._graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self._graph):
                 self._step_body(self._g_ts, self._g_dsig)
+            self.graph_captures = getattr(self, "graph_captures", 0) + 1
         self._g_ts.copy_(ts)
         self._g_dsig.copy_(dsig)
         self._graph.replay()
@@ -236,6 +241,149 @@ class CTSDDenoiser:
         if self.frame_shard is not None:
             out = self.frame_shard.gather_frames(out, 1)               # every rank returns the whole sample
         return out
+
+    # ---- persistent stream session (frame-in / frame-out generation, drivers.StreamingDriver(persistent=True)): what run() rebuilds
+    # for every incoming frame - the latents, the model input, every condition, the cached adapter residuals, the captured graph -
+    # is built ONCE and lives in static device buffers.  A new frame is one dwm_fifo_slide_multi launch over all of them (every
+    # buffer moves by one frame along the time axis and takes the new frame's noise / conditions / residuals at its end) plus the
+    # adapter on the 2B V images of that frame; the whole-step graph keeps replaying, since no address changed.  The steps of the
+    # warm-up, the steady state and the flush differ in the timestep / sigma-step tables alone, which _graph_step refreshes anyway.
+    def begin_stream(self, latents: torch.Tensor, conditions: Dict[str, torch.Tensor], replace_keys=()):
+        """Start a session from the latents [B,T,V,C,H,W] (the queue's noise) and the conditions of its T frames: what
+        prepare(latents, conditions, image_latents=latents, diffusion_forcing=True) sets up, in buffers that survive the frames.
+        Conditions with a frame axis at dim 1 will slide; those of NO_FRAME_AXIS, those named in `replace_keys` (the driver's
+        autoregression_condition_exception_for_take_sequence) and tensors of at most one dimension are replaced wholesale by
+        advance_stream.  A session of the same shapes is already open: its buffers, its slide tables and its graph are reused."""
+        if self.frame_shard is not None or self.cfg_group is not None:
+            raise ValueError("a stream session keeps one sample on one GPU: frame_group / cfg_group sessions are not built")
+        from types import SimpleNamespace
+        dev = latents.device
+        B, T = latents.shape[:2]
+        if self.inference_steps % T != 0:
+            raise ValueError("inference_steps must be a multiple of the frame count in diffusion-forcing mode")
+        cd = getattr(self.model, "compute_dtype", bf16)
+        replaced = set(self.NO_FRAME_AXIS) | set(replace_keys)
+
+        def converted(k, v):
+            return v.to(cd) if torch.is_tensor(v) and v.is_floating_point() and k != "added_time_ids" else v
+        slide_keys = tuple(k for k, v in conditions.items()
+                           if torch.is_tensor(v) and k not in replaced and v.dim() >= 2 and v.shape[1] == T)
+        sig = (str(dev), tuple(latents.shape), cd, slide_keys,
+               tuple((k, tuple(v.shape), cd if v.is_floating_point() and k != "added_time_ids" else v.dtype) if torch.is_tensor(v)
+                     else (k, None, repr(v)) for k, v in conditions.items()))
+        s = self._session
+        if s is not None and s.sig == sig:
+            self.latents.copy_(latents)
+            for k, v in conditions.items():
+                if torch.is_tensor(v):
+                    self.conditions[k].copy_(v)
+            # the cached adapter residuals belong to the condition images just overwritten: recompute them where they are (the
+            # graph and the slide tables hold their addresses)
+            self._hold_adapter_cache(s)
+            if s.cache_feats is not None and not self.model.refill_adapter_cache(self.conditions["condition_image_tensor"]):
+                self._graph, s.plan, s.cache_feats, s.cache_fresh = None, None, None, None
+        else:
+            self._graph = None
+            self.latents = latents.to(torch.float32).contiguous().clone()
+            self.cd = cd
+            self.model_in = torch.empty((2 * B, *latents.shape[1:]), dtype=cd, device=dev)
+            self.conditions = {k: (converted(k, v).contiguous().clone() if torch.is_tensor(v) else v) for k, v in conditions.items()}
+            s = self._session = SimpleNamespace(
+                sig=sig, slide_keys=slide_keys, plan=None, cache_feats=None, cache_fresh=None, cache_step=None,
+                noise=torch.empty((B, 1, *latents.shape[2:]), dtype=torch.float32, device=dev),
+                staging={k: torch.empty_like(self.conditions[k][:, :1]) for k in slide_keys},
+                snapshot=torch.empty_like(self.latents))
+            self._ts_dev = self.schedule.timesteps.to(dev)
+            self._sig_dev = self.schedule.sigmas.to(dev)
+        self.diffusion_forcing, self.take_time = True, 0
+        self.total_frames, self.t0, self.ref, self.image_latents = T, 0, 0, None
+        self.spi = self.inference_steps // T
+        if hasattr(self.model, "frame_shard"):
+            self.model.frame_shard = None
+        self._refresh_model_in()
+        return self
+
+    def _stream(self):
+        if self._session is None:
+            raise RuntimeError("no stream session: begin_stream() first (prepare() / run() end one)")
+        return self._session
+
+    def _hold_adapter_cache(self, s):
+        """The model's cached adapter residuals of the session's condition images slide with the images, and the captured graph
+        reads them at their addresses.  The model's cache has one slot, which any forward with another condition tensor (another
+        driver on the same model) takes over - the residuals it drops would be freed under the graph.  So the session adopts the
+        list once the model has computed it, keeps it alive, and puts it back into the model's slot before every use."""
+        cit = self.conditions.get("condition_image_tensor")
+        if not torch.is_tensor(cit) or "condition_image_tensor" not in s.slide_keys or not hasattr(self.model, "adapter_cache_of"):
+            return
+        from .blocks import STORE
+        if s.cache_feats is None:
+            feats = self.model.adapter_cache_of(cit)
+            if feats is not None:
+                s.cache_feats, s.cache_step, s.plan = feats, STORE.step, None           # (the plan is rebuilt with them in it)
+        elif s.cache_step != STORE.step:                                                # other weights: other residuals, other graph
+            s.cache_feats, s.cache_fresh, s.plan, self._graph = None, None, None, None
+        elif self.model.adapter_cache_of(cit) is not s.cache_feats:
+            self.model.install_adapter_cache(cit, s.cache_feats)
+
+    def _plan_stream_slide(self, s):
+        B, T = self.latents.shape[:2]
+        pairs = [(self.latents, s.noise, B, T), (self.model_in, s.noise, 2 * B, T)]      # both CFG halves take the one noise frame
+        pairs += [(self.conditions[k], s.staging[k], self.conditions[k].shape[0], T) for k in s.slide_keys]
+        s.cache_fresh = None
+        if s.cache_feats is not None:                                                   # per level [2B T V N, D] = [2B][T][V N D]
+            s.cache_fresh = [torch.empty((f.shape[0] // T, f.shape[1]), dtype=f.dtype, device=f.device) for f in s.cache_feats]
+            pairs += [(f, n, self.conditions["condition_image_tensor"].shape[0], T) for f, n in zip(s.cache_feats, s.cache_fresh)]
+        s.plan = ops.FifoSlide(pairs)
+
+    def advance_stream(self, noise_frame: torch.Tensor, frame_conditions: Dict[str, torch.Tensor]):
+        """One frame in: the queue drops its oldest frame and takes `noise_frame` [B,1,V,C,H,W] (fp32, host or device) and the
+        one-frame conditions at its end.  Small copies into static staging buffers, the adapter on the new frame's images if the
+        model caches its residuals, ONE slide launch over every buffer, in-place copies of the replaced conditions."""
+        s = self._stream()
+        s.noise.copy_(noise_frame)
+        for k in s.slide_keys:
+            v = frame_conditions.get(k)
+            if not torch.is_tensor(v) or tuple(v.shape) != tuple(s.staging[k].shape):
+                raise ValueError(f"advance_stream: condition {k!r} of one frame must be a tensor {tuple(s.staging[k].shape)}")
+            s.staging[k].copy_(v)
+        self._hold_adapter_cache(s)
+        if s.plan is None:
+            self._plan_stream_slide(s)
+        if s.cache_fresh is not None:
+            self.model.advance_adapter_cache(s.staging["condition_image_tensor"], out=s.cache_fresh)
+        s.plan.run()
+        self.slide_launches += 1
+        for k, v in frame_conditions.items():
+            if k in s.slide_keys:
+                continue
+            cur = self.conditions.get(k)
+            if torch.is_tensor(v) and torch.is_tensor(cur) and cur.shape == v.shape:
+                cur.copy_(v)
+            elif not torch.is_tensor(v) and not torch.is_tensor(cur) and k in self.conditions:
+                if cur != v:
+                    self.conditions[k], self._graph = v, None                           # a python value is baked into the capture
+            else:
+                raise ValueError(f"advance_stream: condition {k!r} is new or changed its shape: begin a new stream")
+        return self
+
+    def stream_window(self, start: int, stop: int, take_time: int = 0) -> torch.Tensor:
+        """Steps start .. stop - 1 on the session's queue, as run(..., start=, stop=, take_time=) on it; returns a COPY of queue
+        slot `take_time` [B,1,V,C,H,W] (the frame a stream emits: the queue itself is overwritten by the next frame).  In the flush
+        (take_time > 0) the slots up to take_time keep their state of before the window, as the driver's merge does."""
+        s = self._stream()
+        self.take_time = take_time
+        if take_time > 0:
+            s.snapshot.copy_(self.latents)
+        self._hold_adapter_cache(s)
+        for i in range(start, stop):
+            self.step(i)
+        self._hold_adapter_cache(s)                                   # (adopts the residuals the first forward computed)
+        frame = self.latents[:, take_time:take_time + 1].clone()
+        if take_time > 0:
+            self.latents[:, :take_time + 1].copy_(s.snapshot[:, :take_time + 1])
+            self._refresh_model_in()
+        return frame
 
     def run(self, latents: torch.Tensor, conditions: Dict[str, torch.Tensor], stop: Optional[int] = None,
             start: int = 0, **prepare_kw):
