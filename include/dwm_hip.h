@@ -642,6 +642,48 @@ int dwm_groupnorm_bwd(const void* x, const void* dz, void* dx, int64_t I, int64_
                       const void* gamma, const void* beta, int32_t silu, int32_t accumulate, float* stats,
                       float* dgamma, float* dbeta, const dwm_rowmap2d* dz_map, const dwm_gn_imgmap* img_map, void* stream);
 
+/* ----------------------------------------------------------------------
+ * Ordered reductions: the five entry points above that finish their column sums with fp32 atomics, in a form whose result is
+ * a function of the input values, the shapes and the library build only (no dependence on repetition, addresses, cache state or
+ * what else the device runs).  Arguments, checks and status codes of the sibling, plus `workspace` (fp32, 16-byte aligned, need not
+ * be initialised) of at least dwm_<op>_ordered_floats(...) floats: DWM_EINVAL if it is NULL or smaller, DWM_EALIGN if misaligned.
+ * Everything that is not a reduction (dx, accumulate) is bit-equal to the sibling: one kernel body serves both forms.
+ *
+ * Two stages.  1: every workgroup of the sibling's grid writes its per-column partial sums - themselves computed in a fixed order -
+ * to its own workspace row instead of issuing atomics (workgroups with an empty row range write zeros).  2: one more launch adds
+ * the partials of each (group, column) as a plain left fold over ASCENDING chunk index k, starting from +0,
+ *     total = (((0 + P[0]) + P[1]) + ...) + P[n - 1],         then ONCE   out[g][c] += total.
+ * Workspace layout and chunks per op (row-major; cols = ncols / D / C):
+ *   segsum, segsum_diff   P [groups][cpg][ncols]; chunk k of group g = rows [g * rows_per_group + 128 k, + 128) cut at the group's
+ *                         end, cpg = ceil(min(rows_per_group, rows) / 128); fold over k within the group.
+ *   layernorm_bwd         P [slots][groups][cpg][D]; slots = the non-NULL ones of dgamma, dbeta, dgamma2, dbeta2 in that order;
+ *                         groups of rows_per_mod rows (one group of all rows if 0), chunks of 64 rows, cpg = ceil(min(rows per
+ *                         group, rows) / 64).  grad_per_group: fold over k within group g into row g; else over all
+ *                         groups * cpg chunks in memory order (g-major) into row 0.
+ *   rmsnorm_heads_bwd     P [chunks][ncols]; chunk k = rows [32 k, 32 k + 32); fold over all chunks.  (Within a chunk the four waves
+ *                         - rows k*32 + w, + 4, ... for wave w - are added as ((w0 + w1) + w2) + w3.)
+ *   groupnorm_bwd         P [I][chunks][2][C] (row 0 dgamma, row 1 dbeta); chunk = the pixel block of the statistics pass (P split as
+ *                         dwm_groupnorm_stats_floats describes: chunks = dwm_groupnorm_bwd_ordered_floats / (2 * I * C)); fold over
+ *                         all I * chunks blocks in memory order (image-major).
+ * ---------------------------------------------------------------------- */
+int64_t dwm_segsum_ordered_floats(int64_t rows, int64_t ncols, int64_t rows_per_group);
+int64_t dwm_segsum_diff_ordered_floats(int64_t rows, int64_t ncols, int64_t rows_per_group);
+int64_t dwm_layernorm_bwd_ordered_floats(const dwm_layernorm_bwd_args* args);
+int64_t dwm_rmsnorm_heads_bwd_ordered_floats(int64_t rows, int64_t ncols);
+int64_t dwm_groupnorm_bwd_ordered_floats(int64_t I, int64_t P, int32_t C);
+int dwm_segsum_ordered(const void* a, int64_t lda, const void* b, int64_t ldb, int64_t rows, int64_t ncols,
+                       int64_t rows_per_group, float* out, int64_t ld_out, float* workspace, int64_t workspace_floats, void* stream);
+int dwm_segsum_diff_ordered(const void* a, int64_t lda, const void* b, int64_t ldb, const void* b2, int64_t ldb2, int64_t rows,
+                            int64_t ncols, int64_t rows_per_group, float* out, int64_t ld_out, float* workspace,
+                            int64_t workspace_floats, void* stream);
+int dwm_layernorm_bwd_ordered(const dwm_layernorm_bwd_args* args, float* workspace, int64_t workspace_floats, void* stream);
+int dwm_rmsnorm_heads_bwd_ordered(const void* y, int64_t ldy, const float* rinv, const void* w, void* dy, int64_t lddy,
+                                  int64_t rows, int64_t ncols, float* dw, float* workspace, int64_t workspace_floats, void* stream);
+int dwm_groupnorm_bwd_ordered(const void* x, const void* dz, void* dx, int64_t I, int64_t P, int32_t C, int32_t G, float eps,
+                              const void* gamma, const void* beta, int32_t silu, int32_t accumulate, float* stats,
+                              float* dgamma, float* dbeta, const dwm_rowmap2d* dz_map, const dwm_gn_imgmap* img_map,
+                              float* workspace, int64_t workspace_floats, void* stream);
+
 /* Block permutation: dst block (i0, i1, i2, i3) <- src block at i0*sstride[0] + i1*sstride[1] + i2*sstride[2] + i3*sstride[3]
  * (strides in blocks), blocks of `block_bytes` contiguous bytes (a multiple of 16; both buffers 16-byte aligned), dst dense in the
  * order (i0, i1, i2, i3).  The pack / unpack around the frame-shard all-to-all (opendwm_amd/sharding.py: "my frames, all token rows" <->

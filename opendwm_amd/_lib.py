@@ -217,6 +217,18 @@ SIGNATURES = {
     "dwm_cast_bf16_to_f32": (_i32, [_vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp]),
     "dwm_groupnorm_bwd": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _f32, _vp, _vp, _i32, _i32, _vp, _vp, _vp,
                                  C.POINTER(RowMap2D), C.POINTER(GnImgMap), _vp]),
+    # ordered (order-deterministic) reductions: the sibling's arguments + (workspace, workspace_floats); *_floats = the size queries
+    "dwm_segsum_ordered": (_i32, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "dwm_segsum_diff_ordered": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "dwm_layernorm_bwd_ordered": (_i32, [C.POINTER(LayerNormBwdArgs), _vp, _i64, _vp]),
+    "dwm_rmsnorm_heads_bwd_ordered": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "dwm_groupnorm_bwd_ordered": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _f32, _vp, _vp, _i32, _i32, _vp, _vp, _vp,
+                                         C.POINTER(RowMap2D), C.POINTER(GnImgMap), _vp, _i64, _vp]),
+    "dwm_segsum_ordered_floats": (_i64, [_i64, _i64, _i64]),
+    "dwm_segsum_diff_ordered_floats": (_i64, [_i64, _i64, _i64]),
+    "dwm_layernorm_bwd_ordered_floats": (_i64, [C.POINTER(LayerNormBwdArgs)]),
+    "dwm_rmsnorm_heads_bwd_ordered_floats": (_i64, [_i64, _i64]),
+    "dwm_groupnorm_bwd_ordered_floats": (_i64, [_i64, _i64, _i32]),
 }
 
 _ERR = {-1: "DWM_EINVAL (bad shape / null pointer)", -2: "DWM_EALIGN (alignment)",

@@ -225,3 +225,16 @@ inline int dwm_launch_status() {
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? DWM_OK : (int)e;
 }
+
+// ---- stage 2 of the ordered reductions (dwm_*_ordered, train.hip / vae.hip).  Stage 1 left fp32 partials in a workspace; for every
+// slot s < nslots, group g < groups and column c < ncols (ncols % 4 == 0, 16-byte aligned partial rows):
+//   out[s][g * ld_out + c] += (((0 + P(s, g, 0, c)) + P(s, g, 1, c)) + ...) + P(s, g, nfold - 1, c)
+//   P(s, g, k, c) = ws[s][g * group_stride + k * fold_stride + c]
+// i.e. a plain left fold over ascending k, then ONE add into out.  Defined in train.hip; enqueues one launch on `stream`.
+struct DwmFoldArgs {
+    const float* ws[4];
+    float* out[4];
+    int nslots;
+    int64_t nfold, fold_stride, group_stride, groups, ncols, ld_out;
+};
+void dwm_ordered_finish(const DwmFoldArgs& f, hipStream_t stream);

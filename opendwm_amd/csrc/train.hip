@@ -1,6 +1,7 @@
 // Backward-pass / optimizer kernels of the CTSD train step (reference: src/dwm/pipelines/ctsd.py
 // :1195-1437, backward of the modules listed in include/dwm_hip.h).  All HBM-bound: 16-B bf16x8
-// accesses, fp32 arithmetic, reductions accumulated with fp32 atomics into caller-zeroed buffers.
+// accesses, fp32 arithmetic, reductions accumulated with fp32 atomics into caller-zeroed buffers - or, in the ORDERED instantiation
+// of the same kernels (dwm_*_ordered), written as per-workgroup partials and folded in a fixed order by ordered_finish_kernel.
 #include "common.h"
 #include "dwm_hip.h"
 
@@ -60,11 +61,16 @@ transpose8_kernel(const bf16_t* __restrict__ in, int64_t ld_in, int64_t rows, in
 // ---------------------------------------------------------------------------------- segmented sums
 // out[g][n] += sum_{r in group g} a[r][n] * (b ? b[r][n] : 1).  Block = 256 threads = 32 column
 // chunks (8 columns each) x 8 row lanes; a block covers 256 columns x up to RB rows of ONE group.
+// ORDERED (dwm_segsum_ordered / dwm_segsum_diff_ordered): the block's 256 column sums go to row blockIdx.y = g * chunks_per_group + ch
+// of the workspace `ws` [groups * chunks_per_group, ncols] with plain 16-byte stores - empty row ranges included, as zeros - and
+// dwm_ordered_finish adds them into `out`.
 constexpr int SEG_RB = 128;
+template <bool ORDERED>
 __global__ void __launch_bounds__(256)
 segsum_kernel(const bf16_t* __restrict__ a, int64_t lda, const bf16_t* __restrict__ b, int64_t ldb,
               const bf16_t* __restrict__ b2, int64_t ldb2,
-              int64_t rows, int64_t ncols, int64_t rpg, int chunks_per_group, float* __restrict__ out, int64_t ld_out) {
+              int64_t rows, int64_t ncols, int64_t rpg, int chunks_per_group, float* __restrict__ out, int64_t ld_out,
+              float* __restrict__ ws) {
     __shared__ float red[8][256];
     const int cx = threadIdx.x & 31, ry = threadIdx.x >> 5;
     const int64_t g = blockIdx.y / chunks_per_group, ch = blockIdx.y % chunks_per_group;
@@ -97,12 +103,60 @@ segsum_kernel(const bf16_t* __restrict__ a, int64_t lda, const bf16_t* __restric
 #pragma unroll
     for (int j = 0; j < 8; ++j) red[ry][cx * 8 + j] = acc[j];
     __syncthreads();
-    const int col = threadIdx.x;
-    float s = 0.f;
+    if constexpr (ORDERED) {
+        const int64_t c4 = (int64_t)blockIdx.x * 256 + threadIdx.x * 4;
+        if (threadIdx.x < 64 && c4 < ncols) {
+            float s[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int i = 0; i < 8; ++i) s += red[i][col];
-    const int64_t cc = (int64_t)blockIdx.x * 256 + col;
-    if (cc < ncols && rbeg < rend) atomicAdd(out + g * ld_out + cc, s);
+            for (int i = 0; i < 8; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) s[j] += red[i][threadIdx.x * 4 + j];
+            *(float4*)(ws + (int64_t)blockIdx.y * ncols + c4) = make_float4(s[0], s[1], s[2], s[3]);
+        }
+    } else {
+        const int col = threadIdx.x;
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) s += red[i][col];
+        const int64_t cc = (int64_t)blockIdx.x * 256 + col;
+        if (cc < ncols && rbeg < rend) atomicAdd(out + g * ld_out + cc, s);
+    }
+}
+
+// ---------------------------------------------------------------------------------- ordered finish
+// Stage 2 of every ordered reduction (contract: DwmFoldArgs in common.h).  A thread owns 4 adjacent columns of one (slot, group): a
+// wave reads 1 KiB of each partial row, 16 B per lane, FOLD_UNROLL rows requested before the first is added (the fold is a serial
+// chain per column; only the loads overlap), and the running sums stay in registers.  Block = one wave, so that the few columns
+// of a launch (1536 columns = 6 waves per group) spread over as many CUs as there are waves.
+constexpr int FOLD_UNROLL = 32;           // 128 VGPRs of loads in flight per lane: the chain is nfold / 32 memory round trips long
+__global__ void __launch_bounds__(64)
+ordered_finish_kernel(const DwmFoldArgs f) {
+    const int64_t c = ((int64_t)blockIdx.x * 64 + threadIdx.x) * 4;
+    if (c >= f.ncols) return;
+    const int64_t g = blockIdx.y;
+    const float* __restrict__ p = f.ws[blockIdx.z] + g * f.group_stride + c;
+    float t[4] = {0.f, 0.f, 0.f, 0.f};
+    int64_t k = 0;
+    for (; k + FOLD_UNROLL <= f.nfold; k += FOLD_UNROLL) {
+        float4 v[FOLD_UNROLL];
+#pragma unroll
+        for (int u = 0; u < FOLD_UNROLL; ++u) v[u] = *(const float4*)(p + (k + u) * f.fold_stride);
+#pragma unroll
+        for (int u = 0; u < FOLD_UNROLL; ++u) { t[0] += v[u].x; t[1] += v[u].y; t[2] += v[u].z; t[3] += v[u].w; }
+    }
+    for (; k < f.nfold; ++k) {
+        const float4 v = *(const float4*)(p + k * f.fold_stride);
+        t[0] += v.x; t[1] += v.y; t[2] += v.z; t[3] += v.w;
+    }
+    float* __restrict__ o = f.out[blockIdx.z] + g * f.ld_out + c;
+    if ((((uintptr_t)o) & 15u) == 0) {          // a float4 of the accumulator where it is aligned, four floats where it is not
+        float4 a = *(const float4*)o;
+        a.x += t[0]; a.y += t[1]; a.z += t[2]; a.w += t[3];
+        *(float4*)o = a;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] += t[j];
+    }
 }
 
 // ---------------------------------------------------------------------------------- activations
@@ -253,9 +307,12 @@ rowcombine_kernel(const bf16_t* __restrict__ a, int64_t lda, const bf16_t* __res
 // LDS and flushed with one atomic per column and workgroup.
 constexpr int LN_BWD_RB = 64;        // (round 4: 128 -> 64.  One training sample is 43 008 rows = 336 blocks of 128: 1.3 blocks per CU, 32
                                      //  rows per wave one after the other, each a chain of three memory round trips - 219 us for 400 MB)
-template <int NI>
+// ORDERED (dwm_layernorm_bwd_ordered): the flush writes the block's column sums of the s-th non-null accumulator (order dgamma, dbeta,
+// dgamma2, dbeta2) to ws[(s * gridDim.x + blockIdx.x) * D ...] instead - every block, empty row ranges as zeros - for
+// dwm_ordered_finish.  Everything before the flush is the one body of both forms.
+template <int NI, bool ORDERED>
 __global__ void __launch_bounds__(256)
-layernorm_bwd_kernel(const dwm_layernorm_bwd_args p, int chunks_per_group) {
+layernorm_bwd_kernel(const dwm_layernorm_bwd_args p, int chunks_per_group, float* __restrict__ ws) {
     constexpr int RB = LN_BWD_RB;           // rows per block (a quarter per wave)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int D = p.D;
@@ -395,6 +452,7 @@ layernorm_bwd_kernel(const dwm_layernorm_bwd_args p, int chunks_per_group) {
     __shared__ float red[4][NI * 512];
     const int64_t gg = p.grad_per_group ? g : 0;
     float* const outs[4] = {p.dgamma, p.dbeta, p.dgamma2, p.dbeta2};
+    int slot = 0;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         if (outs[q] == nullptr) continue;               // kernel-argument uniform
@@ -405,9 +463,20 @@ layernorm_bwd_kernel(const dwm_layernorm_bwd_args p, int chunks_per_group) {
             for (int j = 0; j < 8; ++j)
                 red[wave][(i * 64 + lane) * 8 + j] = q == 0 ? sg[i][j] : q == 1 ? sb[i][j] : q == 2 ? sg2[i][j] : sb2[i][j];
         __syncthreads();
-        for (int c = threadIdx.x; c < D; c += 256) {
-            const float v = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
-            if (rbeg < rend) atomicAdd(outs[q] + gg * p.ld_grad + c, v);
+        if constexpr (ORDERED) {
+            float* __restrict__ wrow = ws + ((int64_t)slot * gridDim.x + blockIdx.x) * D;
+            for (int c = threadIdx.x * 4; c < D; c += 1024) {
+                float v[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] = (red[0][c + j] + red[1][c + j]) + (red[2][c + j] + red[3][c + j]);
+                *(float4*)(wrow + c) = make_float4(v[0], v[1], v[2], v[3]);
+            }
+            ++slot;
+        } else {
+            for (int c = threadIdx.x; c < D; c += 256) {
+                const float v = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
+                if (rbeg < rend) atomicAdd(outs[q] + gg * p.ld_grad + c, v);
+            }
         }
     }
 }
@@ -440,44 +509,72 @@ rmsnorm_heads_train_kernel(bf16_t* __restrict__ x, int64_t ldx, int64_t rows, in
 
 // backward in place on dy (-> dx); y = normalised output (xhat * w), rinv from the forward.
 // dw[c] += sum_rows dy * xhat (fp32 atomics; block-local LDS reduction first).
+// ORDERED (dwm_rmsnorm_heads_bwd_ordered): no atomics.  The columns are walked in tiles of RMS_ORD_TILE; each wave puts its sums of a
+// tile into its own LDS row (every slot is written: a wave without rows writes zeros), the rows are added as ((w0 + w1) + w2) + w3
+// and the result goes to row blockIdx.x of the workspace `ws` [blocks, ncols] for dwm_ordered_finish.  The default form is the
+// same body with one tile = all columns.
+constexpr int RMS_ORD_TILE = 4096;        // columns per tile of the ordered form: 4 LDS rows = 64 KiB
+template <bool ORDERED>
 __global__ void __launch_bounds__(256)
 rmsnorm_heads_bwd_kernel(const bf16_t* __restrict__ y, int64_t ldy, const float* __restrict__ rinv,
                          const bf16_t* __restrict__ w, bf16_t* __restrict__ dy, int64_t lddy,
-                         int64_t rows, int64_t ncols, float* __restrict__ dw) {
-    extern __shared__ float dwl[];            // [ncols]
-    for (int i = threadIdx.x; i < ncols; i += 256) dwl[i] = 0.f;
-    __syncthreads();
+                         int64_t rows, int64_t ncols, float* __restrict__ dw, float* __restrict__ ws) {
+    extern __shared__ float dwl[];            // [ncols]; ORDERED: [4][tile]
+    const int64_t tile = ORDERED && ncols > RMS_ORD_TILE ? RMS_ORD_TILE : ncols;
+    if constexpr (!ORDERED) {
+        for (int i = threadIdx.x; i < ncols; i += 256) dwl[i] = 0.f;
+        __syncthreads();
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t nh = ncols / 64;
     const int64_t rbeg = (int64_t)blockIdx.x * 32;
-    for (int64_t c = lane * 8; c < ncols; c += 512) {
-        float wv[8], acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        unpack8(*(const uint4*)(w + c), wv);
-        for (int64_t row = rbeg + wave; row < rbeg + 32 && row < rows; row += 4) {
-            float yv[8], d[8], xh[8], dxh[8];
-            unpack8(*(const uint4*)(y + row * ldy + c), yv);
-            unpack8(*(const uint4*)(dy + row * lddy + c), d);
-            float m = 0.f;
+    for (int64_t c0 = 0; c0 < ncols; c0 += tile) {          // block-uniform; one trip in the default form
+        const int64_t cend = c0 + tile < ncols ? c0 + tile : ncols;
+        for (int64_t c = c0 + lane * 8; c < cend; c += 512) {
+            float wv[8], acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            unpack8(*(const uint4*)(w + c), wv);
+            for (int64_t row = rbeg + wave; row < rbeg + 32 && row < rows; row += 4) {
+                float yv[8], d[8], xh[8], dxh[8];
+                unpack8(*(const uint4*)(y + row * ldy + c), yv);
+                unpack8(*(const uint4*)(dy + row * lddy + c), d);
+                float m = 0.f;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                xh[j] = wv[j] != 0.f ? yv[j] / wv[j] : 0.f;
-                acc[j] += d[j] * xh[j];
-                dxh[j] = d[j] * wv[j];
-                m += dxh[j] * xh[j];
+                for (int j = 0; j < 8; ++j) {
+                    xh[j] = wv[j] != 0.f ? yv[j] / wv[j] : 0.f;
+                    acc[j] += d[j] * xh[j];
+                    dxh[j] = d[j] * wv[j];
+                    m += dxh[j] * xh[j];
+                }
+                m += __shfl_xor(m, 1, 64); m += __shfl_xor(m, 2, 64); m += __shfl_xor(m, 4, 64);
+                m *= 1.f / 64.f;
+                const float ri = rinv[row * nh + c / 64];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) d[j] = ri * (dxh[j] - xh[j] * m);
+                *(uint4*)(dy + row * lddy + c) = pack8(d);
             }
-            m += __shfl_xor(m, 1, 64); m += __shfl_xor(m, 2, 64); m += __shfl_xor(m, 4, 64);
-            m *= 1.f / 64.f;
-            const float ri = rinv[row * nh + c / 64];
+            if constexpr (ORDERED) {
+                float* const l = dwl + wave * tile + (c - c0);
+                *(float4*)l = make_float4(acc[0], acc[1], acc[2], acc[3]);
+                *(float4*)(l + 4) = make_float4(acc[4], acc[5], acc[6], acc[7]);
+            } else {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) d[j] = ri * (dxh[j] - xh[j] * m);
-            *(uint4*)(dy + row * lddy + c) = pack8(d);
+                for (int j = 0; j < 8; ++j) atomicAdd(&dwl[c + j], acc[j]);
+            }
         }
+        __syncthreads();
+        if constexpr (ORDERED) {
+            for (int64_t i = threadIdx.x * 4; i < cend - c0; i += 1024) {
+                float v[4];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) atomicAdd(&dwl[c + j], acc[j]);
+                for (int j = 0; j < 4; ++j) v[j] = ((dwl[i + j] + dwl[tile + i + j]) + dwl[2 * tile + i + j]) + dwl[3 * tile + i + j];
+                *(float4*)(ws + (int64_t)blockIdx.x * ncols + c0 + i) = make_float4(v[0], v[1], v[2], v[3]);
+            }
+            __syncthreads();                               // the next tile overwrites the rows
+        } else {
+            for (int i = threadIdx.x; i < ncols; i += 256)
+                if (dwl[i] != 0.f) atomicAdd(dw + i, dwl[i]);
+        }
     }
-    __syncthreads();
-    for (int i = threadIdx.x; i < ncols; i += 256)
-        if (dwl[i] != 0.f) atomicAdd(dw + i, dwl[i]);
 }
 
 // ---------------------------------------------------------------------------------- optimizer / casts
@@ -779,8 +876,8 @@ extern "C" int dwm_segsum(const void* a, int64_t lda, const void* b, int64_t ldb
     const int cpg = (int)((rpg + SEG_RB - 1) / SEG_RB);
     if (groups * cpg >= 65536 * 16) return DWM_EUNSUPPORTED;
     const dim3 grid((unsigned)((ncols + 255) / 256), (unsigned)(groups * cpg));
-    hipLaunchKernelGGL(segsum_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, lda, (const bf16_t*)b, ldb,
-                       (const bf16_t*)nullptr, (int64_t)0, rows, ncols, rows_per_group, cpg, out, ld_out);
+    hipLaunchKernelGGL(segsum_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, lda, (const bf16_t*)b, ldb,
+                       (const bf16_t*)nullptr, (int64_t)0, rows, ncols, rows_per_group, cpg, out, ld_out, (float*)nullptr);
     return dwm_launch_status();
 }
 
@@ -793,9 +890,61 @@ extern "C" int dwm_segsum_diff(const void* a, int64_t lda, const void* b, int64_
     const int cpg = (int)((rpg + SEG_RB - 1) / SEG_RB);
     if (groups * cpg >= 65536 * 16) return DWM_EUNSUPPORTED;
     const dim3 grid((unsigned)((ncols + 255) / 256), (unsigned)(groups * cpg));
-    hipLaunchKernelGGL(segsum_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, lda, (const bf16_t*)b, ldb,
-                       (const bf16_t*)b2, ldb2, rows, ncols, rows_per_group, cpg, out, ld_out);
+    hipLaunchKernelGGL(segsum_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, lda, (const bf16_t*)b, ldb,
+                       (const bf16_t*)b2, ldb2, rows, ncols, rows_per_group, cpg, out, ld_out, (float*)nullptr);
     return dwm_launch_status();
+}
+
+// ---- stage 2 of every ordered reduction, also called from vae.hip (declared in common.h)
+void dwm_ordered_finish(const DwmFoldArgs& f, hipStream_t stream) {
+    const dim3 grid((unsigned)((f.ncols / 4 + 63) / 64), (unsigned)f.groups, (unsigned)f.nslots);
+    hipLaunchKernelGGL(ordered_finish_kernel, grid, dim3(64), 0, stream, f);
+}
+
+// ---- ordered forms of the two segmented sums: stage 1 = segsum_kernel<true> into the workspace, stage 2 = dwm_ordered_finish
+extern "C" int64_t dwm_segsum_ordered_floats(int64_t rows, int64_t ncols, int64_t rows_per_group) {
+    if (rows <= 0 || ncols <= 0 || rows_per_group <= 0) return 0;
+    const int64_t groups = (rows + rows_per_group - 1) / rows_per_group;
+    const int64_t rpg = rows_per_group < rows ? rows_per_group : rows;
+    return groups * ((rpg + SEG_RB - 1) / SEG_RB) * ncols;
+}
+extern "C" int64_t dwm_segsum_diff_ordered_floats(int64_t rows, int64_t ncols, int64_t rows_per_group) {
+    return dwm_segsum_ordered_floats(rows, ncols, rows_per_group);
+}
+
+static int segsum_ordered_launch(const void* a, int64_t lda, const void* b, int64_t ldb, const void* b2, int64_t ldb2, int64_t rows,
+                                 int64_t ncols, int64_t rows_per_group, float* out, int64_t ld_out, float* workspace,
+                                 int64_t workspace_floats, void* stream) {
+    if (!workspace || workspace_floats < dwm_segsum_ordered_floats(rows, ncols, rows_per_group)) return DWM_EINVAL;
+    if (!dwm_aligned16(workspace)) return DWM_EALIGN;
+    const int64_t groups = (rows + rows_per_group - 1) / rows_per_group;
+    const int64_t rpg = rows_per_group < rows ? rows_per_group : rows;
+    const int cpg = (int)((rpg + SEG_RB - 1) / SEG_RB);
+    if (groups * cpg >= 65536 * 16 || groups >= 65536) return DWM_EUNSUPPORTED;
+    const dim3 grid((unsigned)((ncols + 255) / 256), (unsigned)(groups * cpg));
+    hipLaunchKernelGGL(segsum_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, lda, (const bf16_t*)b, ldb,
+                       (const bf16_t*)b2, ldb2, rows, ncols, rows_per_group, cpg, out, ld_out, workspace);
+    DwmFoldArgs f = {};
+    f.ws[0] = workspace; f.out[0] = out; f.nslots = 1;
+    f.nfold = cpg; f.fold_stride = ncols; f.group_stride = (int64_t)cpg * ncols; f.groups = groups; f.ncols = ncols; f.ld_out = ld_out;
+    dwm_ordered_finish(f, (hipStream_t)stream);
+    return dwm_launch_status();
+}
+
+extern "C" int dwm_segsum_ordered(const void* a, int64_t lda, const void* b, int64_t ldb, int64_t rows, int64_t ncols,
+                                  int64_t rows_per_group, float* out, int64_t ld_out, float* workspace, int64_t workspace_floats,
+                                  void* stream) {
+    if (!a || !out || rows <= 0 || ncols <= 0 || ncols % 8 != 0 || rows_per_group <= 0) return DWM_EINVAL;
+    if (lda % 8 != 0 || (b && ldb % 8 != 0) || !dwm_aligned16(a) || (b && !dwm_aligned16(b))) return DWM_EALIGN;
+    return segsum_ordered_launch(a, lda, b, ldb, nullptr, 0, rows, ncols, rows_per_group, out, ld_out, workspace, workspace_floats, stream);
+}
+
+extern "C" int dwm_segsum_diff_ordered(const void* a, int64_t lda, const void* b, int64_t ldb, const void* b2, int64_t ldb2,
+                                       int64_t rows, int64_t ncols, int64_t rows_per_group, float* out, int64_t ld_out,
+                                       float* workspace, int64_t workspace_floats, void* stream) {
+    if (!a || !b || !b2 || !out || rows <= 0 || ncols <= 0 || ncols % 8 != 0 || rows_per_group <= 0) return DWM_EINVAL;
+    if (lda % 8 != 0 || ldb % 8 != 0 || ldb2 % 8 != 0 || !dwm_aligned16(a) || !dwm_aligned16(b) || !dwm_aligned16(b2)) return DWM_EALIGN;
+    return segsum_ordered_launch(a, lda, b, ldb, b2, ldb2, rows, ncols, rows_per_group, out, ld_out, workspace, workspace_floats, stream);
 }
 
 extern "C" int dwm_act_fwd(const void* x, void* y, int64_t n, int32_t act, void* stream) {
@@ -885,10 +1034,57 @@ extern "C" int dwm_layernorm_bwd(const dwm_layernorm_bwd_args* a, void* stream) 
     hipStream_t s = (hipStream_t)stream;
     const int ni = (a->D + 511) / 512;
     switch (ni) {
-        case 1: hipLaunchKernelGGL(layernorm_bwd_kernel<1>, grid, dim3(256), 0, s, *a, cpg); break;
-        case 2: hipLaunchKernelGGL(layernorm_bwd_kernel<2>, grid, dim3(256), 0, s, *a, cpg); break;
-        case 3: hipLaunchKernelGGL(layernorm_bwd_kernel<3>, grid, dim3(256), 0, s, *a, cpg); break;
-        default: hipLaunchKernelGGL(layernorm_bwd_kernel<4>, grid, dim3(256), 0, s, *a, cpg); break;
+        case 1: hipLaunchKernelGGL((layernorm_bwd_kernel<1, false>), grid, dim3(256), 0, s, *a, cpg, (float*)nullptr); break;
+        case 2: hipLaunchKernelGGL((layernorm_bwd_kernel<2, false>), grid, dim3(256), 0, s, *a, cpg, (float*)nullptr); break;
+        case 3: hipLaunchKernelGGL((layernorm_bwd_kernel<3, false>), grid, dim3(256), 0, s, *a, cpg, (float*)nullptr); break;
+        default: hipLaunchKernelGGL((layernorm_bwd_kernel<4, false>), grid, dim3(256), 0, s, *a, cpg, (float*)nullptr); break;
+    }
+    return dwm_launch_status();
+}
+
+static int ln_bwd_slots(const dwm_layernorm_bwd_args* a) {
+    return (a->dgamma != nullptr) + (a->dbeta != nullptr) + (a->dgamma2 != nullptr) + (a->dbeta2 != nullptr);
+}
+
+extern "C" int64_t dwm_layernorm_bwd_ordered_floats(const dwm_layernorm_bwd_args* a) {
+    if (!a || a->rows <= 0 || a->D <= 0) return 0;
+    const int64_t rpg = a->rows_per_mod > 0 ? a->rows_per_mod : a->rows;
+    const int64_t groups = (a->rows + rpg - 1) / rpg;
+    const int64_t cpg = ((rpg < a->rows ? rpg : a->rows) + LN_BWD_RB - 1) / LN_BWD_RB;
+    return ln_bwd_slots(a) * groups * cpg * a->D;
+}
+
+extern "C" int dwm_layernorm_bwd_ordered(const dwm_layernorm_bwd_args* a, float* workspace, int64_t workspace_floats, void* stream) {
+    if (!a || !a->x || !a->dy || !a->dx || a->rows <= 0 || a->D <= 0 || a->D % 8 != 0 || a->D > 2048) return DWM_EINVAL;
+    if (a->ldx % 8 != 0 || a->lddy % 8 != 0 || a->lddx % 8 != 0 || (a->dy2 && a->lddy2 % 8 != 0)) return DWM_EALIGN;
+    if ((a->scale || a->scale2) && (a->rows_per_mod <= 0 || a->ld_mod % 8 != 0)) return DWM_EINVAL;
+    if (a->addvec && (a->rows_per_add <= 0 || a->ld_add % 8 != 0)) return DWM_EINVAL;
+    if ((a->dgamma || a->dbeta || a->dgamma2 || a->dbeta2) && a->ld_grad < a->D) return DWM_EINVAL;
+    const int nslots = ln_bwd_slots(a);
+    if (nslots > 0 && (!workspace || workspace_floats < dwm_layernorm_bwd_ordered_floats(a))) return DWM_EINVAL;
+    if (nslots > 0 && !dwm_aligned16(workspace)) return DWM_EALIGN;
+    const int64_t rpg = a->rows_per_mod > 0 ? a->rows_per_mod : a->rows;
+    const int64_t groups = (a->rows + rpg - 1) / rpg;
+    const int cpg = (int)(((rpg < a->rows ? rpg : a->rows) + LN_BWD_RB - 1) / LN_BWD_RB);
+    if (groups * cpg >= (1ll << 31) || (a->grad_per_group && groups >= 65536)) return DWM_EUNSUPPORTED;
+    const dim3 grid((unsigned)(groups * cpg));
+    hipStream_t s = (hipStream_t)stream;
+    const int ni = (a->D + 511) / 512;
+    switch (ni) {
+        case 1: hipLaunchKernelGGL((layernorm_bwd_kernel<1, true>), grid, dim3(256), 0, s, *a, cpg, workspace); break;
+        case 2: hipLaunchKernelGGL((layernorm_bwd_kernel<2, true>), grid, dim3(256), 0, s, *a, cpg, workspace); break;
+        case 3: hipLaunchKernelGGL((layernorm_bwd_kernel<3, true>), grid, dim3(256), 0, s, *a, cpg, workspace); break;
+        default: hipLaunchKernelGGL((layernorm_bwd_kernel<4, true>), grid, dim3(256), 0, s, *a, cpg, workspace); break;
+    }
+    if (nslots > 0) {
+        DwmFoldArgs f = {};
+        float* const outs[4] = {a->dgamma, a->dbeta, a->dgamma2, a->dbeta2};
+        for (int q = 0; q < 4; ++q)
+            if (outs[q]) { f.ws[f.nslots] = workspace + (int64_t)f.nslots * groups * cpg * a->D; f.out[f.nslots++] = outs[q]; }
+        f.fold_stride = a->D; f.ncols = a->D; f.ld_out = a->ld_grad;
+        if (a->grad_per_group) { f.nfold = cpg; f.group_stride = (int64_t)cpg * a->D; f.groups = groups; }
+        else { f.nfold = groups * cpg; f.group_stride = 0; f.groups = 1; }
+        dwm_ordered_finish(f, s);
     }
     return dwm_launch_status();
 }
@@ -906,8 +1102,31 @@ extern "C" int dwm_rmsnorm_heads_bwd(const void* y, int64_t ldy, const float* ri
                                      int64_t rows, int64_t ncols, float* dw, void* stream) {
     if (!y || !rinv || !w || !dy || !dw || rows <= 0 || ncols <= 0 || ncols % 64 != 0 || ncols > 8192) return DWM_EINVAL;
     if (ldy % 8 != 0 || lddy % 8 != 0 || !dwm_aligned16(y) || !dwm_aligned16(dy) || !dwm_aligned16(w)) return DWM_EALIGN;
-    hipLaunchKernelGGL(rmsnorm_heads_bwd_kernel, dim3((unsigned)((rows + 31) / 32)), dim3(256), (size_t)ncols * sizeof(float),
-                       (hipStream_t)stream, (const bf16_t*)y, ldy, rinv, (const bf16_t*)w, (bf16_t*)dy, lddy, rows, ncols, dw);
+    hipLaunchKernelGGL(rmsnorm_heads_bwd_kernel<false>, dim3((unsigned)((rows + 31) / 32)), dim3(256), (size_t)ncols * sizeof(float),
+                       (hipStream_t)stream, (const bf16_t*)y, ldy, rinv, (const bf16_t*)w, (bf16_t*)dy, lddy, rows, ncols, dw,
+                       (float*)nullptr);
+    return dwm_launch_status();
+}
+
+extern "C" int64_t dwm_rmsnorm_heads_bwd_ordered_floats(int64_t rows, int64_t ncols) {
+    return rows <= 0 || ncols <= 0 ? 0 : (rows + 31) / 32 * ncols;
+}
+
+extern "C" int dwm_rmsnorm_heads_bwd_ordered(const void* y, int64_t ldy, const float* rinv, const void* w, void* dy, int64_t lddy,
+                                             int64_t rows, int64_t ncols, float* dw, float* workspace, int64_t workspace_floats,
+                                             void* stream) {
+    if (!y || !rinv || !w || !dy || !dw || rows <= 0 || ncols <= 0 || ncols % 64 != 0 || ncols > 8192) return DWM_EINVAL;
+    if (ldy % 8 != 0 || lddy % 8 != 0 || !dwm_aligned16(y) || !dwm_aligned16(dy) || !dwm_aligned16(w)) return DWM_EALIGN;
+    if (!workspace || workspace_floats < dwm_rmsnorm_heads_bwd_ordered_floats(rows, ncols)) return DWM_EINVAL;
+    if (!dwm_aligned16(workspace)) return DWM_EALIGN;
+    const int64_t blocks = (rows + 31) / 32;
+    const size_t lds = 4 * (size_t)(ncols > RMS_ORD_TILE ? RMS_ORD_TILE : ncols) * sizeof(float);
+    hipLaunchKernelGGL(rmsnorm_heads_bwd_kernel<true>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)y,
+                       ldy, rinv, (const bf16_t*)w, (bf16_t*)dy, lddy, rows, ncols, dw, workspace);
+    DwmFoldArgs f = {};
+    f.ws[0] = workspace; f.out[0] = dw; f.nslots = 1;
+    f.nfold = blocks; f.fold_stride = ncols; f.group_stride = 0; f.groups = 1; f.ncols = ncols; f.ld_out = ncols;
+    dwm_ordered_finish(f, (hipStream_t)stream);
     return dwm_launch_status();
 }
 

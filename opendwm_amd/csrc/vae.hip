@@ -276,10 +276,14 @@ DWM_DEVINL float silu_grad_f(float y, float dz) {
     return dz * sg * (1.f + y * (1.f - sg));
 }
 
+// ORDERED (dwm_groupnorm_bwd_ordered): no atomics; block b = i * gridDim.x + blockIdx.x writes its channel sums to the workspace `ws`
+// [I * chunks][2][C] (row 0: dgamma, row 1: dbeta) with 16-byte stores and dwm_ordered_finish folds the blocks in ascending b.
+template <bool ORDERED>
 __global__ void __launch_bounds__(256)
 gn_bwd_stats_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dz, int64_t P, int C, int G, int64_t ppb,
                     const float* __restrict__ fstats, const bf16_t* __restrict__ gamma, const bf16_t* __restrict__ beta, float eps,
-                    int silu, float* __restrict__ part, float* __restrict__ dgamma, float* __restrict__ dbeta, PadMap pm, ImgMap im) {
+                    int silu, float* __restrict__ part, float* __restrict__ dgamma, float* __restrict__ dbeta, PadMap pm, ImgMap im,
+                    float* __restrict__ ws) {
     extern __shared__ float red[];            // [pstep][C8][4] group partials, then [pstep][C][2] channel partials
     const int i = blockIdx.y;
     const int C8 = C >> 3, CG = C / G;
@@ -346,11 +350,23 @@ gn_bwd_stats_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dz,
         float* o = part + (((int64_t)i * gridDim.x + blockIdx.x) * G + g) * 2;
         o[0] = a; o[1] = b;
     }
-    for (int c = threadIdx.x; c < C; c += 256) {
-        float sg = 0.f, sb = 0.f;
-        for (int pr = 0; pr < pstep; ++pr) { sg += red2[((size_t)pr * C + c) * 2]; sb += red2[((size_t)pr * C + c) * 2 + 1]; }
-        atomicAdd(dgamma + c, sg);
-        atomicAdd(dbeta + c, sb);
+    if constexpr (ORDERED) {
+        float* __restrict__ wrow = ws + ((int64_t)i * gridDim.x + blockIdx.x) * 2 * C;
+        for (int c = threadIdx.x * 4; c < C; c += 1024) {
+            float sg[4] = {0.f, 0.f, 0.f, 0.f}, sb[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int pr = 0; pr < pstep; ++pr)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { sg[j] += red2[((size_t)pr * C + c + j) * 2]; sb[j] += red2[((size_t)pr * C + c + j) * 2 + 1]; }
+            *(float4*)(wrow + c) = make_float4(sg[0], sg[1], sg[2], sg[3]);
+            *(float4*)(wrow + C + c) = make_float4(sb[0], sb[1], sb[2], sb[3]);
+        }
+    } else {
+        for (int c = threadIdx.x; c < C; c += 256) {
+            float sg = 0.f, sb = 0.f;
+            for (int pr = 0; pr < pstep; ++pr) { sg += red2[((size_t)pr * C + c) * 2]; sb += red2[((size_t)pr * C + c) * 2 + 1]; }
+            atomicAdd(dgamma + c, sg);
+            atomicAdd(dbeta + c, sb);
+        }
     }
 }
 
@@ -478,9 +494,17 @@ static int groupnorm_impl(const void* x, void* y, int64_t I, int64_t P, int32_t 
     return dwm_launch_status();
 }
 
-extern "C" int dwm_groupnorm_bwd(const void* x, const void* dz, void* dx, int64_t I, int64_t P, int32_t C, int32_t G, float eps,
-                                 const void* gamma, const void* beta, int32_t silu, int32_t accumulate, float* stats,
-                                 float* dgamma, float* dbeta, const dwm_rowmap2d* dz_map, const dwm_gn_imgmap* img_map, void* stream) {
+extern "C" int64_t dwm_groupnorm_bwd_ordered_floats(int64_t I, int64_t P, int32_t C) {
+    if (I <= 0 || P <= 0 || C <= 0) return 0;
+    const int64_t ppb = gn_pixels_per_block(I, P);
+    return I * ((P + ppb - 1) / ppb) * 2 * C;
+}
+
+// both forms of the GroupNorm backward: `ordered` picks stage 1 into `workspace` + dwm_ordered_finish over the atomics
+static int groupnorm_bwd_impl(const void* x, const void* dz, void* dx, int64_t I, int64_t P, int32_t C, int32_t G, float eps,
+                              const void* gamma, const void* beta, int32_t silu, int32_t accumulate, float* stats,
+                              float* dgamma, float* dbeta, const dwm_rowmap2d* dz_map, const dwm_gn_imgmap* img_map, bool ordered,
+                              float* workspace, int64_t workspace_floats, void* stream) {
     if (x == nullptr || dz == nullptr || dx == nullptr || gamma == nullptr || beta == nullptr || stats == nullptr || dgamma == nullptr ||
         dbeta == nullptr)
         return DWM_EINVAL;
@@ -488,6 +512,8 @@ extern "C" int dwm_groupnorm_bwd(const void* x, const void* dz, void* dx, int64_
     const int CG = C / G;
     if (C % 8 != 0 || !(CG == 4 || CG >= 8) || I > 65535 || I * P >= (1ll << 31)) return DWM_EUNSUPPORTED;
     if (!dwm_aligned16(x) || !dwm_aligned16(dz) || !dwm_aligned16(dx) || !dwm_aligned16(gamma) || !dwm_aligned16(beta)) return DWM_EALIGN;
+    if (ordered && (workspace == nullptr || workspace_floats < dwm_groupnorm_bwd_ordered_floats(I, P, C))) return DWM_EINVAL;
+    if (ordered && !dwm_aligned16(workspace)) return DWM_EALIGN;
     ImgMap im;
     im.enabled = img_map != nullptr && img_map->iv > 0;
     if (im.enabled) {
@@ -522,14 +548,40 @@ extern "C" int dwm_groupnorm_bwd(const void* x, const void* dz, void* dx, int64_
     const dim3 grid((unsigned)nchunks, (unsigned)I);
     hipLaunchKernelGGL(gn_stats_kernel<bf16_t>, grid, dim3(256), lds_f, s, (const bf16_t*)x, P, C, G, ppb, fpart, im);
     hipLaunchKernelGGL(gn_finalize_kernel, dim3((unsigned)I), dim3(64), 0, s, (const float*)fpart, fstats, nchunks, 2 * G);
-    hipLaunchKernelGGL(gn_bwd_stats_kernel, grid, dim3(256), lds_b, s, (const bf16_t*)x, (const bf16_t*)dz, P, C, G, ppb,
-                       (const float*)fstats, (const bf16_t*)gamma, (const bf16_t*)beta, eps, silu, bpart, dgamma, dbeta, pm, im);
+    if (ordered) {
+        hipLaunchKernelGGL(gn_bwd_stats_kernel<true>, grid, dim3(256), lds_b, s, (const bf16_t*)x, (const bf16_t*)dz, P, C, G, ppb,
+                           (const float*)fstats, (const bf16_t*)gamma, (const bf16_t*)beta, eps, silu, bpart, dgamma, dbeta, pm, im,
+                           workspace);
+        DwmFoldArgs f = {};
+        f.ws[0] = workspace; f.ws[1] = workspace + C; f.out[0] = dgamma; f.out[1] = dbeta; f.nslots = 2;
+        f.nfold = I * nchunks; f.fold_stride = 2 * (int64_t)C; f.group_stride = 0; f.groups = 1; f.ncols = C; f.ld_out = C;
+        dwm_ordered_finish(f, s);
+    } else {
+        hipLaunchKernelGGL(gn_bwd_stats_kernel<false>, grid, dim3(256), lds_b, s, (const bf16_t*)x, (const bf16_t*)dz, P, C, G, ppb,
+                           (const float*)fstats, (const bf16_t*)gamma, (const bf16_t*)beta, eps, silu, bpart, dgamma, dbeta, pm, im,
+                           (float*)nullptr);
+    }
     hipLaunchKernelGGL(gn_finalize_kernel, dim3((unsigned)I), dim3(64), 0, s, (const float*)bpart, bstats, nchunks, 2 * G);
     const int64_t total = I * P * (C / 8);
     hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)dz,
                        (bf16_t*)dx, I, P, C, G, (const float*)fstats, (const float*)bstats, (const bf16_t*)gamma, (const bf16_t*)beta,
                        eps, silu, accumulate, pm, im);
     return dwm_launch_status();
+}
+
+extern "C" int dwm_groupnorm_bwd(const void* x, const void* dz, void* dx, int64_t I, int64_t P, int32_t C, int32_t G, float eps,
+                                 const void* gamma, const void* beta, int32_t silu, int32_t accumulate, float* stats,
+                                 float* dgamma, float* dbeta, const dwm_rowmap2d* dz_map, const dwm_gn_imgmap* img_map, void* stream) {
+    return groupnorm_bwd_impl(x, dz, dx, I, P, C, G, eps, gamma, beta, silu, accumulate, stats, dgamma, dbeta, dz_map, img_map, false,
+                              nullptr, 0, stream);
+}
+
+extern "C" int dwm_groupnorm_bwd_ordered(const void* x, const void* dz, void* dx, int64_t I, int64_t P, int32_t C, int32_t G, float eps,
+                                         const void* gamma, const void* beta, int32_t silu, int32_t accumulate, float* stats,
+                                         float* dgamma, float* dbeta, const dwm_rowmap2d* dz_map, const dwm_gn_imgmap* img_map,
+                                         float* workspace, int64_t workspace_floats, void* stream) {
+    return groupnorm_bwd_impl(x, dz, dx, I, P, C, G, eps, gamma, beta, silu, accumulate, stats, dgamma, dbeta, dz_map, img_map, true,
+                              workspace, workspace_floats, stream);
 }
 
 extern "C" int dwm_groupnorm_silu_mapped(const void* x, void* y, int64_t I, int64_t P, int32_t C, int32_t G, float eps,

@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import functools
 import os
 import threading
 from dataclasses import dataclass
@@ -471,9 +472,55 @@ def gemm_4wave_scope(on: bool):
         _G4W.on = prev
 
 
+# Ordered gradient reductions: inside `ordered_reductions(True)` the five reducing wrappers of opendwm_amd.train_ops
+# launch the dwm_*_ordered entry points.  Per thread and carried into the backward exactly like the GEMM scope above.
+_ORD = threading.local()
+
+
+def ordered_reductions_enabled() -> bool:
+    return bool(getattr(_ORD, "on", False))
+
+
+@contextlib.contextmanager
+def ordered_reductions(on: bool):
+    prev = ordered_reductions_enabled()
+    _ORD.on = bool(on)
+    try:
+        yield
+    finally:
+        _ORD.on = prev
+
+
+def opens_ordered_scope(fn):
+    """decorator for a training forward fn(model, ...): it runs inside ordered_reductions(model.ordered_reductions) - a plain
+    attribute, False where it is absent (CTSDTrainer(deterministic=...) sets it)"""
+    @functools.wraps(fn)
+    def wrapped(model, *args, **kwargs):
+        with ordered_reductions(getattr(model, "ordered_reductions", False)):
+            return fn(model, *args, **kwargs)
+    return wrapped
+
+
+def carries_ordered_scope(cls):
+    """class decorator for torch.autograd.Function subclasses: the backward (autograd's own thread) runs inside the
+    ordered_reductions scope its forward ran in"""
+    fwd, bwd = cls.forward, cls.backward
+
+    def forward(ctx, *args, **kwargs):
+        ctx._ordered_reductions = ordered_reductions_enabled()
+        return fwd(ctx, *args, **kwargs)
+
+    def backward(ctx, *grads):
+        with ordered_reductions(getattr(ctx, "_ordered_reductions", False)):
+            return bwd(ctx, *grads)
+
+    cls.forward, cls.backward = staticmethod(forward), staticmethod(backward)
+    return cls
+
+
 def carries_gemm_scope(cls):
     """class decorator for torch.autograd.Function subclasses: the backward (autograd's own thread) runs inside the
-    gemm_4wave_scope its forward ran in"""
+    gemm_4wave_scope and the ordered_reductions scope its forward ran in"""
     fwd, bwd = cls.forward, cls.backward
 
     def forward(ctx, *args, **kwargs):
@@ -485,7 +532,7 @@ def carries_gemm_scope(cls):
             return bwd(ctx, *grads)
 
     cls.forward, cls.backward = staticmethod(forward), staticmethod(backward)
-    return cls
+    return carries_ordered_scope(cls)
 
 
 _SPLIT_WEIGHTS: dict = {}

@@ -974,6 +974,7 @@ class RayEmbFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------ model forward
+@ops.opens_ordered_scope
 def forward_train(model, sample, timestep, encoder_hidden_states, pooled_projections, disable_crossview=None,
                   disable_temporal=None, crossview_attention_mask=None, added_time_ids=None, condition_image_tensor=None,
                   camera_intrinsics_norm=None, camera2referego=None):

@@ -11,6 +11,7 @@ import torch
 
 from . import _lib, ops, quant8
 from .ops import _call, _chk2d, _p, cast_f32, ACT_GELU_TANH, ACT_SILU  # noqa: F401  (cast_f32: fp32 (+)= bf16, used as train_ops.cast_f32)
+from .ops import ordered_reductions, ordered_reductions_enabled, carries_ordered_scope  # noqa: F401  (the scope lives beside the GEMM scope)
 
 bf16 = torch.bfloat16
 # weight gradients by dwm_gemm_tn (operands as they are); "0": the transposes + NT GEMM path (A/B measurements)
@@ -29,9 +30,18 @@ def transpose(x: torch.Tensor, rows_pad: Optional[int] = None, out: Optional[tor
     return out
 
 
+# ---- ordered reductions (include/dwm_hip.h, "Ordered reductions").  Inside `ordered_reductions(True)` the five reducing
+# wrappers below launch dwm_<op>_ordered with a workspace from the caching allocator (uninitialised: stage 1 writes every slot stage 2
+# reads).  `return_partials=True` (tests) makes a wrapper return (result, partials): the workspace viewed as [chunks..., cols] with
+# the op's documented layout, None outside the scope.
+def _ordered_workspace(query: str, dev: torch.device, *args) -> torch.Tensor:
+    return torch.empty(max(int(getattr(_lib.load(), query)(*args)), 1), dtype=torch.float32, device=dev)
+
+
 def segsum(a: torch.Tensor, b: Optional[torch.Tensor] = None, rows_per_group: Optional[int] = None,
-           out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """fp32 [groups, ncols]: per-group column sums of a (* b); `out` (if given) is accumulated into."""
+           out: Optional[torch.Tensor] = None, return_partials: bool = False):
+    """fp32 [groups, ncols]: per-group column sums of a (* b); `out` (if given) is accumulated into.
+    return_partials: (out, partials [groups, chunks, ncols]) inside ordered_reductions, (out, None) outside."""
     _chk2d(a, "a")
     rows, ncols = a.shape
     rpg = rows if rows_per_group is None else rows_per_group
@@ -40,22 +50,40 @@ def segsum(a: torch.Tensor, b: Optional[torch.Tensor] = None, rows_per_group: Op
         out = torch.zeros((groups, ncols), dtype=torch.float32, device=a.device)
     if b is not None:
         _chk2d(b, "b")
-    _call("dwm_segsum", _p(a), a.stride(0), _p(b), 0 if b is None else b.stride(0), rows, ncols, rpg, _p(out), out.stride(0))
-    return out
+    ws = None
+    if ordered_reductions_enabled():
+        ws = _ordered_workspace("dwm_segsum_ordered_floats", a.device, rows, ncols, rpg)
+        _call("dwm_segsum_ordered", _p(a), a.stride(0), _p(b), 0 if b is None else b.stride(0), rows, ncols, rpg, _p(out),
+              out.stride(0), _p(ws), ws.numel())
+        ws = ws.view(groups, -1, ncols)
+    else:
+        _call("dwm_segsum", _p(a), a.stride(0), _p(b), 0 if b is None else b.stride(0), rows, ncols, rpg, _p(out), out.stride(0))
+    return (out, ws) if return_partials else out
 
 
-def segsum_diff(a: torch.Tensor, b: torch.Tensor, b2: torch.Tensor, rows_per_group: Optional[int] = None) -> torch.Tensor:
-    """fp32 [groups, ncols]: per-group column sums of a * (b - b2), the difference taken in fp32 before the product."""
+def segsum_diff(a: torch.Tensor, b: torch.Tensor, b2: torch.Tensor, rows_per_group: Optional[int] = None,
+                out: Optional[torch.Tensor] = None, return_partials: bool = False):
+    """fp32 [groups, ncols]: per-group column sums of a * (b - b2), the difference taken in fp32 before the product; `out` (if given)
+    is accumulated into.  return_partials: as segsum."""
     for t, n in ((a, "a"), (b, "b"), (b2, "b2")):
         _chk2d(t, n)
     if b.shape != a.shape or b2.shape != a.shape:
         raise RuntimeError("segsum_diff: shape mismatch")
     rows, ncols = a.shape
     rpg = rows if rows_per_group is None else rows_per_group
-    out = torch.zeros(((rows + rpg - 1) // rpg, ncols), dtype=torch.float32, device=a.device)
-    _call("dwm_segsum_diff", _p(a), a.stride(0), _p(b), b.stride(0), _p(b2), b2.stride(0), rows, ncols, rpg,
-          _p(out), out.stride(0))
-    return out
+    groups = (rows + rpg - 1) // rpg
+    if out is None:
+        out = torch.zeros((groups, ncols), dtype=torch.float32, device=a.device)
+    ws = None
+    if ordered_reductions_enabled():
+        ws = _ordered_workspace("dwm_segsum_diff_ordered_floats", a.device, rows, ncols, rpg)
+        _call("dwm_segsum_diff_ordered", _p(a), a.stride(0), _p(b), b.stride(0), _p(b2), b2.stride(0), rows, ncols, rpg,
+              _p(out), out.stride(0), _p(ws), ws.numel())
+        ws = ws.view(groups, -1, ncols)
+    else:
+        _call("dwm_segsum_diff", _p(a), a.stride(0), _p(b), b.stride(0), _p(b2), b2.stride(0), rows, ncols, rpg,
+              _p(out), out.stride(0))
+    return (out, ws) if return_partials else out
 
 
 def act_fwd(x: torch.Tensor, act: int) -> torch.Tensor:
@@ -143,8 +171,10 @@ def layernorm_bwd(x: torch.Tensor, dy: torch.Tensor, *, eps: float, dx: Optional
                   scale2: Optional[torch.Tensor] = None, rows_per_mod: int = 0, dy2: Optional[torch.Tensor] = None,
                   dgamma: Optional[torch.Tensor] = None, dbeta: Optional[torch.Tensor] = None,
                   dgamma2: Optional[torch.Tensor] = None, dbeta2: Optional[torch.Tensor] = None,
-                  grad_per_group: bool = False) -> torch.Tensor:
-    """Backward of ops.layernorm; dgamma/dbeta[/2] are fp32 [G or 1, D] accumulators (see dwm_layernorm_bwd)."""
+                  grad_per_group: bool = False, return_partials: bool = False):
+    """Backward of ops.layernorm; dgamma/dbeta[/2] are fp32 [G or 1, D] accumulators (see dwm_layernorm_bwd).
+    return_partials: (dx, partials [slots, groups, chunks, D]) inside ordered_reductions - slots = the accumulators given, in the
+    order dgamma, dbeta, dgamma2, dbeta2 - and (dx, None) outside or without accumulators."""
     _chk2d(x, "x"); _chk2d(dy, "dy")
     rows, D = x.shape
     if dx is None:
@@ -167,8 +197,17 @@ def layernorm_bwd(x: torch.Tensor, dy: torch.Tensor, *, eps: float, dx: Optional
     if g0 is not None:
         a.dgamma, a.dbeta, a.dgamma2, a.dbeta2 = _p(dgamma), _p(dbeta), _p(dgamma2), _p(dbeta2)
         a.ld_grad, a.grad_per_group = g0.stride(0), int(grad_per_group)
-    _call("dwm_layernorm_bwd", C.byref(a))
-    return dx
+    ws = None
+    if ordered_reductions_enabled():
+        ws = _ordered_workspace("dwm_layernorm_bwd_ordered_floats", x.device, C.byref(a))
+        _call("dwm_layernorm_bwd_ordered", C.byref(a), _p(ws), ws.numel())
+        slots = sum(g is not None for g in (dgamma, dbeta, dgamma2, dbeta2))
+        rpg = rows_per_mod if rows_per_mod > 0 else rows
+        groups = (rows + rpg - 1) // rpg
+        ws = ws.view(slots, groups, -1, D) if slots else None
+    else:
+        _call("dwm_layernorm_bwd", C.byref(a))
+    return (dx, ws) if return_partials else dx
 
 
 def rmsnorm_heads_train_(x: torch.Tensor, w_expanded: torch.Tensor, eps: float) -> torch.Tensor:
@@ -181,12 +220,20 @@ def rmsnorm_heads_train_(x: torch.Tensor, w_expanded: torch.Tensor, eps: float) 
 
 
 def rmsnorm_heads_bwd_(y: torch.Tensor, rinv: torch.Tensor, w_expanded: torch.Tensor, dy: torch.Tensor,
-                       dw: torch.Tensor) -> torch.Tensor:
-    """dy -> dx in place; dw fp32 [ncols] accumulated."""
+                       dw: torch.Tensor, return_partials: bool = False):
+    """dy -> dx in place; dw fp32 [ncols] accumulated.
+    return_partials: (dx, partials [chunks of 32 rows, ncols]) inside ordered_reductions, (dx, None) outside."""
     _chk2d(y, "y"); _chk2d(dy, "dy")
     rows, ncols = y.shape
-    _call("dwm_rmsnorm_heads_bwd", _p(y), y.stride(0), _p(rinv), _p(w_expanded), _p(dy), dy.stride(0), rows, ncols, _p(dw))
-    return dy
+    ws = None
+    if ordered_reductions_enabled():
+        ws = _ordered_workspace("dwm_rmsnorm_heads_bwd_ordered_floats", y.device, rows, ncols)
+        _call("dwm_rmsnorm_heads_bwd_ordered", _p(y), y.stride(0), _p(rinv), _p(w_expanded), _p(dy), dy.stride(0), rows, ncols, _p(dw),
+              _p(ws), ws.numel())
+        ws = ws.view(-1, ncols)
+    else:
+        _call("dwm_rmsnorm_heads_bwd", _p(y), y.stride(0), _p(rinv), _p(w_expanded), _p(dy), dy.stride(0), rows, ncols, _p(dw))
+    return (dy, ws) if return_partials else dy
 
 
 # ---- tensor lists: AdamW, 8-bit AdamW and the gradient norm share one scheme.  A list of tensors is cut into chunks of `chunk` elements,
@@ -441,10 +488,11 @@ def conv_wgrad(dy: torch.Tensor, x_pad: torch.Tensor, idx: torch.Tensor, shifts)
 
 def groupnorm_bwd(x: torch.Tensor, dz: torch.Tensor, I: int, P: int, gamma: torch.Tensor, beta: torch.Tensor, groups: int,
                   eps: float, dgamma: torch.Tensor, dbeta: torch.Tensor, *, silu: bool = True, dx: Optional[torch.Tensor] = None,
-                  accumulate: bool = False, dz_grid=None, img_map: Optional[tuple] = None) -> torch.Tensor:
+                  accumulate: bool = False, dz_grid=None, img_map: Optional[tuple] = None, return_partials: bool = False):
     """Backward of ops.groupnorm_silu: x [I*P, C] = the forward input, dz = gradient of the forward output - compact
     rows, or (dz_grid) the padded grid the forward wrote into; returns dx [I*P, C] bf16 (accumulate: added to the given dx);
-    dgamma / dbeta: fp32 [C] accumulators (see dwm_groupnorm_bwd)."""
+    dgamma / dbeta: fp32 [C] accumulators (see dwm_groupnorm_bwd).
+    return_partials: (dx, partials [I, chunks, 2, C]; [..., 0, :] dgamma, [..., 1, :] dbeta) inside ordered_reductions, else (dx, None)."""
     _chk2d(x, "x")
     _chk2d(dz, "dz")
     Cc = x.shape[1]
@@ -463,6 +511,13 @@ def groupnorm_bwd(x: torch.Tensor, dz: torch.Tensor, I: int, P: int, gamma: torc
         raise RuntimeError("groupnorm_bwd: bad dx")
     stats = torch.empty(2 * _lib.load().dwm_groupnorm_stats_floats(I, P, groups), dtype=torch.float32, device=x.device)
     m, im = ops._gn_maps(dz_grid, img_map)
-    _call("dwm_groupnorm_bwd", _p(x), _p(dz), _p(dx), I, P, Cc, groups, eps, _p(gamma), _p(beta), int(silu), int(accumulate),
-          _p(stats), _p(dgamma), _p(dbeta), C.byref(m), C.byref(im))
-    return dx
+    ws = None
+    if ordered_reductions_enabled():
+        ws = _ordered_workspace("dwm_groupnorm_bwd_ordered_floats", x.device, I, P, Cc)
+        _call("dwm_groupnorm_bwd_ordered", _p(x), _p(dz), _p(dx), I, P, Cc, groups, eps, _p(gamma), _p(beta), int(silu),
+              int(accumulate), _p(stats), _p(dgamma), _p(dbeta), C.byref(m), C.byref(im), _p(ws), ws.numel())
+        ws = ws.view(I, -1, 2, Cc)
+    else:
+        _call("dwm_groupnorm_bwd", _p(x), _p(dz), _p(dx), I, P, Cc, groups, eps, _p(gamma), _p(beta), int(silu), int(accumulate),
+              _p(stats), _p(dgamma), _p(dbeta), C.byref(m), C.byref(im))
+    return (dx, ws) if return_partials else dx

@@ -175,6 +175,7 @@ def temporal_resnet_backward(G: Grads, tb: UM.TemporalResnetBlock, s: torch.Tens
     return ds, dtp, dalpha
 
 
+@ops.carries_ordered_scope
 class ResBlockFn(torch.autograd.Function):
     """dwm.models.crossview_temporal.ResBlock (:75-164): ResnetBlock2D [+ TemporalResnetBlock, AlphaBlender].
     Gradient-carrying inputs: x, silu_emb [I, E], alpha [B]."""
@@ -315,6 +316,7 @@ def basic_block_backward(G: Grads, blk: UM.BasicTransformerBlock, h: torch.Tenso
     return dh
 
 
+@ops.carries_ordered_scope
 class BasicBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, blk, n_img, ctx_rows, h, *params):
@@ -332,6 +334,7 @@ class BasicBlockFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------ TransformerModel ends
+@ops.carries_ordered_scope
 class TMInFn(torch.autograd.Function):
     """TransformerModel head: GroupNorm(32, eps 1e-6) -> proj_in"""
 
@@ -356,6 +359,7 @@ class TMInFn(torch.autograd.Function):
         return (None, None, dx) + _grads_for(G, ps, ctx.needs_input_grad[3:])
 
 
+@ops.carries_ordered_scope
 class TMOutFn(torch.autograd.Function):
     """TransformerModel tail: proj_out(h) + x"""
 
@@ -400,6 +404,7 @@ def transformer_model_train(tm: UM.TransformerModel, x, ctx_rows, g: UM._Geom, d
 
 
 # ------------------------------------------------------------------------------------------ samplers, stem, head
+@ops.carries_ordered_scope
 class DownsampleFn(torch.autograd.Function):
     """Downsample2D(padding=1): 3x3 stride-2 convolution with symmetric padding"""
 
@@ -438,6 +443,7 @@ class DownsampleFn(torch.autograd.Function):
         return (None, None, None, None, dx) + _grads_for(G, _params(conv), ctx.needs_input_grad[5:])
 
 
+@ops.carries_ordered_scope
 class UpsampleFn(torch.autograd.Function):
     """Upsample2D: nearest 2x, then a 3x3 convolution"""
 
@@ -470,6 +476,7 @@ class UpsampleFn(torch.autograd.Function):
         return (None, None, None, None, dx) + _grads_for(G, _params(conv), ctx.needs_input_grad[5:])
 
 
+@ops.carries_ordered_scope
 class ConvInFn(torch.autograd.Function):
     """conv_in on the NCHW latents (no gradient to the latents)"""
 
@@ -498,6 +505,7 @@ class ConvInFn(torch.autograd.Function):
         return (None, None) + _grads_for(G, _params(conv), ctx.needs_input_grad[2:])
 
 
+@ops.carries_ordered_scope
 class HeadFn(torch.autograd.Function):
     """conv_norm_out (GroupNorm + SiLU) -> conv_out -> NCHW"""
 
@@ -537,6 +545,7 @@ class HeadFn(torch.autograd.Function):
         return (None, None, dx) + _grads_for(G, ps, ctx.needs_input_grad[3:])
 
 
+@ops.carries_ordered_scope
 class ConcatFn(torch.autograd.Function):
     """torch.cat([a, b], channel) on token-major rows"""
 
@@ -553,6 +562,7 @@ class ConcatFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------ model forward
+@ops.opens_ordered_scope
 def forward_train(model: UM.UNetCrossviewTemporalConditionModel, sample, timesteps, encoder_hidden_states=None,
                   disable_crossview=None, disable_temporal=None, crossview_attention_mask=None, added_time_ids=None,
                   condition_image_tensor=None):
