@@ -778,6 +778,48 @@ int dwm_unpatchify_f32(const float* x, int64_t ldx, int64_t I, int32_t C, int32_
 int dwm_cfg_euler_step_f32(const float* pred, float* latents, float* model_in, int64_t n, float guidance, float dsigma,
                            const float* dsigma_group, int64_t group_elems, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Text encoders (opendwm_amd/text_encoders.py): the frozen CLIP-L / CLIP-G / T5-XXL encoders `get_conditions` calls
+ * (src/dwm/pipelines/ctsd.py:186-192, :205-253, :744-804; in the reference: transformers CLIPTextModel,
+ * CLIPTextModelWithProjection and T5EncoderModel).  Their linear layers are dwm_gemm_bf16, CLIP's norms dwm_layernorm_x32;
+ * below is what those do not cover.  bf16 path only.
+ *
+ * dwm_text_attention: out[s*L + i, h*64 + d] = sum_j softmax_j(x_ij) v[s*L + j, h*64 + d],
+ *   x_ij = scale * <q[s*L + i, h*64 ..], k[s*L + j, h*64 ..]> + (bias ? bias[h, i, j] : 0),  j in [0, L) and, with causal = 1,
+ *   j <= i.  bf16 q / k / v / out, fp32 scores and softmax (natural-log domain).  q, k, v share the row stride ld (elements; they
+ *   may be the three column blocks of one fused [n_seq*L, 3*heads*64] buffer), out has ldo.  bias: fp32 [heads, L, L], shared by
+ *   all sequences, or NULL (T5: scale 1 and its relative-position bias; CLIP: scale 1/8, causal, no bias; neither encoder takes
+ *   a padding mask on this path).  Head width 64.  1 <= L <= 128, else DWM_EUNSUPPORTED - checked before anything else is looked
+ *   at; a row's <= 128 scores stay in registers, so the row maximum is exact (no online rescaling).  Keys >= L and causally
+ *   excluded keys are removed by selection (their weight is exactly 0), nothing outside rows [0, n_seq*L) is read or written.
+ *   Deterministic (no atomics).  Null pointers / sizes <= 0 / ld < heads*64: DWM_EINVAL; pointers off 16 bytes or strides not a
+ *   multiple of 8 elements: DWM_EALIGN. */
+typedef struct dwm_text_attn_args {
+    const void* q; const void* k; const void* v; int64_t ld;
+    void* out; int64_t ldo;
+    int64_t n_seq, L;
+    int32_t heads; float scale; int32_t causal;
+    const float* bias;
+} dwm_text_attn_args;
+int dwm_text_attention(const dwm_text_attn_args* args, void* stream);
+
+/* T5LayerNorm over whole rows: y[r, :] = x[r, :] * rsqrt(mean(x[r, :]^2) + eps) * w - no mean subtraction, no bias.  x: the fp32
+ * residual stream [rows, D] (row stride ldx, fp32 elements), w: bf16 [D], y: bf16 (row stride ldy); statistics in fp32.
+ * D % 8 == 0 and D <= 8192, else DWM_EUNSUPPORTED. */
+int dwm_rmsnorm_rows(const float* x, int64_t ldx, int64_t rows, int64_t D, const void* w_bf16, float eps, void* y_bf16, int64_t ldy,
+                     void* stream);
+
+/* out[i, :] = table[ids[i], :] (+ pos[i % L, :] if pos != NULL), i < n: the token (and CLIP position) embedding, written as the
+ * fp32 residual stream (row stride ldo).  ids: int64 on the device; table bf16 [vocab, D], pos bf16 [>= L, D], D % 8 == 0.  An id
+ * outside [0, vocab) is clamped into it before an address is formed (the Python wrapper rejects such ids where it can see them). */
+int dwm_text_embed(const int64_t* ids, int64_t n, const void* table_bf16, int64_t vocab, int64_t D, const void* pos_table_bf16,
+                   int64_t L, float* out, int64_t ldo, void* stream);
+
+/* y[r, j] = act(x[r, j]) (gated = 0, x [rows, F]) or act(x[r, j]) * x[r, F + j] (gated = 1, x [rows, 2F]: one wi_0|wi_1 GEMM, then
+ * this), j < F; bf16 in / out, computed in fp32.  kind 0: quick-GELU x sigmoid(1.702 x) (CLIP-L); 1: erf-GELU (CLIP-G, the SD 2.1
+ * CLIP); 2: tanh-GELU (T5's gelu_new).  F % 8 == 0. */
+int dwm_text_act(const void* x, int64_t ldx, int64_t rows, int64_t F, int32_t kind, int32_t gated, void* y, int64_t ldy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -126,6 +126,11 @@ class VaeAttnArgs(C.Structure):
                 ("I", _i64), ("P", _i64), ("C", _i32), ("scale", _f32)]
 
 
+class TextAttnArgs(C.Structure):
+    _fields_ = [("q", _vp), ("k", _vp), ("v", _vp), ("ld", _i64), ("out", _vp), ("ldo", _i64), ("n_seq", _i64), ("L", _i64),
+                ("heads", _i32), ("scale", _f32), ("causal", _i32), ("bias", _vp)]
+
+
 # name -> (restype, argtypes); every symbol include/dwm_hip.h declares
 SIGNATURES = {
     "dwm_abi_version": (_i32, []),
@@ -229,6 +234,11 @@ SIGNATURES = {
     "dwm_layernorm_bwd_ordered_floats": (_i64, [C.POINTER(LayerNormBwdArgs)]),
     "dwm_rmsnorm_heads_bwd_ordered_floats": (_i64, [_i64, _i64]),
     "dwm_groupnorm_bwd_ordered_floats": (_i64, [_i64, _i64, _i32]),
+    # text encoders
+    "dwm_text_attention": (_i32, [C.POINTER(TextAttnArgs), _vp]),
+    "dwm_rmsnorm_rows": (_i32, [_vp, _i64, _i64, _i64, _vp, _f32, _vp, _i64, _vp]),
+    "dwm_text_embed": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "dwm_text_act": (_i32, [_vp, _i64, _i64, _i64, _i32, _i32, _vp, _i64, _vp]),
 }
 
 _ERR = {-1: "DWM_EINVAL (bad shape / null pointer)", -2: "DWM_EALIGN (alignment)",

@@ -1,11 +1,16 @@
 """The model kwargs of one batch - the caller's side of the hot path: everything `CrossviewTemporalSD.get_conditions`
-(src/dwm/pipelines/ctsd.py:159-453) derives from a dataset batch EXCEPT the text encoders, which stay outside this
-package (the boundary takes embedded text).  Pure host-side tensor logic on whatever device the batch
-lives on; the classifier-free-guidance doubling puts the unconditional half first, as the reference does.
+(src/dwm/pipelines/ctsd.py:159-453) derives from a dataset batch.  The text encoders are part of the package
+(opendwm_amd/text_encoders.py: CLIP and T5 on the HIP path; `encode_sd3_text` / `encode_clip_text` below run them and
+assemble their outputs); what stays with the caller is TOKENISATION - host string code whose vocabulary files do not ship
+here - so the boundary takes token ids, or, as before, embedded text.  Everything else is pure host-side tensor logic on
+whatever device the batch lives on; the classifier-free-guidance doubling puts the unconditional half first, as the
+reference does.
 
     flatten_clip_text        ctsd.py:39-82     nested per-sample / per-frame / per-view prompts -> flat list (+ "" for CFG)
     assemble_sd3_text        ctsd.py:219-253   the two CLIP embeddings padded to the T5 width and stacked with T5
     assemble_clip_text       ctsd.py:186-203   SD 2.1: one CLIP embedding per prompt, repeated or unflattened
+    encode_sd3_text          ctsd.py:205-253   token ids -> CLIP-L / CLIP-G / T5 on the device -> assemble_sd3_text
+    encode_clip_text         ctsd.py:186-203   token ids -> the SD 2.1 CLIP on the device -> assemble_clip_text
     camera_transform_ids     ctsd.py:85-95     intrinsics / image size and extrinsic entries picked by index lists
     action_ids               ctsd.py:97-156    speed [km/h] and steering from consecutive ego poses (-1000 = unconditioned)
     build_conditions         ctsd.py:255-453   layout images (3-D boxes + HD map, unconditional colour), added_time_ids,
@@ -80,6 +85,23 @@ def assemble_clip_text(text_embeddings: torch.Tensor, parsed_shape, sequence_len
     if len(parsed_shape) == 1:
         return text_embeddings[:, None, None].repeat(1, sequence_length, view_count, 1, 1)
     return text_embeddings.unflatten(0, parsed_shape)
+
+
+def encode_sd3_text(encoders, ids_clip_l: torch.Tensor, ids_clip_g: torch.Tensor, ids_t5: Optional[torch.Tensor], parsed_shape,
+                    sequence_length: int, view_count: int, dtype, dedupe: bool = True):
+    """The SD 3 text branch of get_conditions (ctsd.py:205-253) from TOKEN IDS: `encoders` is a text_encoders.SD3TextEncoders, the
+    ids are those of the flat prompt list of `flatten_clip_text` under the three tokenizers (padding="max_length", 77 tokens,
+    truncation - the caller's job: no tokenizer or vocabulary ships with this package), `parsed_shape` is that function's second
+    result.  -> (encoder_hidden_states [B', T, V, L, D], pooled_projections [B', T, V, P]) by way of assemble_sd3_text."""
+    clip, pooled, t5 = encoders.encode(ids_clip_l, ids_clip_g, ids_t5, dedupe=dedupe)
+    return assemble_sd3_text(clip, pooled, t5, parsed_shape, sequence_length, view_count, dtype)
+
+
+def encode_clip_text(text_encoder, ids: torch.Tensor, parsed_shape, sequence_length: int, view_count: int) -> torch.Tensor:
+    """The SD 2.1 text branch (ctsd.py:186-203) from token ids of the flat prompt list: `text_encoder` is a
+    text_encoders.CLIPTextModel, its `[0]` (last_hidden_state) is what the reference takes.  Tokenisation stays with the caller.
+    -> encoder_hidden_states [B', T, V, 77, D] by way of assemble_clip_text."""
+    return assemble_clip_text(text_encoder(ids)[0], parsed_shape, sequence_length, view_count)
 
 
 def camera_transform_ids(batch: Dict, common_config: dict) -> torch.Tensor:

@@ -1285,6 +1285,107 @@ def vae_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.
     return out
 
 
+# ------------------------------------------------------------------------ text encoders
+TEXT_ATTENTION_MAX_L = 128                       # a row's scores stay in registers (dwm_text_attention)
+TEXT_ACT_KINDS = {"quick_gelu": 0, "gelu": 1, "gelu_new": 2, "gelu_pytorch_tanh": 2}
+
+
+def text_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, n_seq: int, L: int, heads: int, scale: float,
+                   causal: bool = False, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = softmax(scale q k^T [+ bias] [causal]) v for n_seq sequences of L tokens, `heads` heads of width 64 (dwm_text_attention).
+    q, k, v: bf16 [n_seq*L, heads*64] with contiguous rows and ONE row stride (column blocks of a fused QKV buffer); bias: fp32
+    [heads, L, L] or None.  L outside 1..TEXT_ATTENTION_MAX_L or another head width: NotImplementedError."""
+    if not 1 <= L <= TEXT_ATTENTION_MAX_L:
+        raise NotImplementedError(f"text_attention: L = {L} is outside 1..{TEXT_ATTENTION_MAX_L}")
+    if heads <= 0 or q.shape[-1] != heads * 64:
+        raise NotImplementedError(f"text_attention: head width {q.shape[-1]} / {heads} is not 64")
+    if n_seq <= 0:
+        raise RuntimeError(f"text_attention: n_seq must be positive, got {n_seq}")
+    for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        _chk2d(t, name)
+        if tuple(t.shape) != (n_seq * L, heads * 64):
+            raise RuntimeError(f"text_attention: {name} must be [n_seq*L, heads*64] = [{n_seq * L}, {heads * 64}], got {tuple(t.shape)}")
+    if not (q.stride(0) == k.stride(0) == v.stride(0)):
+        raise RuntimeError("text_attention: q, k, v must share a row stride")
+    if any(_overlaps(out, t) for t in (q, k, v)):
+        raise RuntimeError("text_attention: out must not overlap q, k or v")
+    _chkvec(bias, "bias", f32)
+    if bias is not None and tuple(bias.shape) != (heads, L, L):
+        raise RuntimeError(f"text_attention: bias must be [heads, L, L] = [{heads}, {L}, {L}], got {tuple(bias.shape)}")
+    a = _lib.TextAttnArgs()
+    a.q, a.k, a.v, a.ld, a.out, a.ldo = q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(0), out.data_ptr(), out.stride(0)
+    a.n_seq, a.L, a.heads, a.scale, a.causal, a.bias = n_seq, L, heads, float(scale), int(bool(causal)), _p(bias)
+    _call("dwm_text_attention", C.byref(a))
+    return out
+
+
+def rmsnorm_rows(x: torch.Tensor, weight: torch.Tensor, eps: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """T5LayerNorm of the fp32 residual stream x [rows, D] -> bf16 (dwm_rmsnorm_rows): x rsqrt(mean(x^2) + eps) weight"""
+    _chk2d(x, "x", f32)
+    _chkvec(weight, "weight")
+    rows, D = x.shape
+    if weight.numel() != D:
+        raise RuntimeError(f"rmsnorm_rows: weight must have {D} elements, got {weight.numel()}")
+    if D % 8 != 0 or D > 8192:
+        raise NotImplementedError(f"rmsnorm_rows: D = {D} must be a multiple of 8, at most 8192")
+    if out is None:
+        out = torch.empty((rows, D), dtype=bf16, device=x.device)
+    _chk2d(out, "out")
+    if out.shape != x.shape:
+        raise RuntimeError("rmsnorm_rows: out must have the shape of x")
+    _call("dwm_rmsnorm_rows", x.data_ptr(), x.stride(0), rows, D, weight.data_ptr(), float(eps), out.data_ptr(), out.stride(0))
+    return out
+
+
+def text_embed(ids: torch.Tensor, table: torch.Tensor, pos: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 stream [n_seq*L, D] = table[ids] (+ pos[position]) for ids [n_seq, L] int64 (dwm_text_embed).  Ids that arrive on the
+    host - the normal case: the tokenizer runs there - are checked against the vocabulary here; ids already on the device are
+    clamped by the kernel instead (checking them would cost a synchronisation)."""
+    if ids.dim() != 2 or ids.dtype != torch.int64:
+        raise RuntimeError(f"text_embed: ids must be a 2-D int64 tensor, got {tuple(ids.shape)} {ids.dtype}")
+    if table.dim() != 2 or ids.numel() == 0:
+        raise RuntimeError(f"text_embed: expected a 2-D table and at least one id, got {tuple(table.shape)}, {tuple(ids.shape)}")
+    vocab, D = table.shape
+    n_seq, L = ids.shape
+    if not ids.is_cuda and (int(ids.min()) < 0 or int(ids.max()) >= vocab):
+        raise ValueError(f"text_embed: token ids outside [0, {vocab}): min {int(ids.min())}, max {int(ids.max())}")
+    _chk2d(table, "table")
+    ids = ids.to(table.device)
+    if not table.is_contiguous() or D % 8 != 0:
+        raise RuntimeError("text_embed: the table must be contiguous with D % 8 == 0")
+    if pos is not None:
+        _chk2d(pos, "pos")
+        if not pos.is_contiguous() or pos.shape[1] != D or pos.shape[0] < L:
+            raise RuntimeError(f"text_embed: pos must be a contiguous [>= {L}, {D}] table, got {tuple(pos.shape)}")
+    ids = ids.contiguous()
+    if out is None:
+        out = torch.empty((n_seq * L, D), dtype=f32, device=table.device)
+    _chk2d(out, "out", f32)
+    if tuple(out.shape) != (n_seq * L, D):
+        raise RuntimeError("text_embed: out must be [n_seq*L, D]")
+    _call("dwm_text_embed", ids.data_ptr(), n_seq * L, table.data_ptr(), vocab, D, _p(pos), L, out.data_ptr(), out.stride(0))
+    return out
+
+
+def text_act(x: torch.Tensor, kind: str, gated: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """act(x) (x [rows, F]) or act(x[:, :F]) * x[:, F:] (gated, x [rows, 2F]) on bf16, computed in fp32 (dwm_text_act);
+    kind: a key of TEXT_ACT_KINDS (the transformers activation names)"""
+    if kind not in TEXT_ACT_KINDS:
+        raise NotImplementedError(f"text_act: activation {kind!r} is not one of {sorted(TEXT_ACT_KINDS)}")
+    _chk2d(x, "x")
+    rows, cols = x.shape
+    F = cols // 2 if gated else cols
+    if (gated and cols % 2) or F % 8 != 0:
+        raise RuntimeError(f"text_act: {cols} columns do not make {'2 x ' if gated else ''}F with F % 8 == 0")
+    if out is None:
+        out = torch.empty((rows, F), dtype=bf16, device=x.device)
+    _chk2d(out, "out")
+    if tuple(out.shape) != (rows, F):
+        raise RuntimeError("text_act: out must be [rows, F]")
+    _call("dwm_text_act", x.data_ptr(), x.stride(0), rows, F, TEXT_ACT_KINDS[kind], int(bool(gated)), out.data_ptr(), out.stride(0))
+    return out
+
+
 def cast_bf16(x: torch.Tensor) -> torch.Tensor:
     if x.dtype == bf16:
         return x
