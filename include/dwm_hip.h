@@ -820,6 +820,49 @@ int dwm_text_embed(const int64_t* ids, int64_t n, const void* table_bf16, int64_
  * CLIP); 2: tanh-GELU (T5's gelu_new).  F % 8 == 0. */
 int dwm_text_act(const void* x, int64_t ldx, int64_t rows, int64_t F, int32_t kind, int32_t gated, void* y, int64_t ldy, void* stream);
 
+/* ------------------------------------------------------------------------
+ * NF4 4-bit weights (opendwm_amd/nf4.py, csrc/gemm_nf4.hip): the `load_in_4bit`, `bnb_4bit_quant_type="nf4"` option of the text
+ * encoders.  The format:
+ *   code    16 sorted fp32 values in [-1, 1], the NF4 data type of the QLoRA paper (Dettmers et al. 2023).  DATA: every entry
+ *           point takes the table by device pointer, none is compiled in.
+ *   blocks  64 consecutive elements along K of one row of a [N, K] weight share one fp32 absmax = the largest |w| of the block
+ *           (a bf16 value held as fp32).  K % 64 == 0.
+ *   codes   with mid[i] = fl32((code[i] + code[i+1]) / 2), i < 15, the code of w is the number of i with fl32(mid[i] * absmax) < w
+ *           (strict: a tie goes to the lower code; no division anywhere, so every implementation of the rule agrees bit for
+ *           bit).  A block with absmax == 0 holds code 7 (the table's 0.0) everywhere.
+ *   packing q: uint8 [N, K/2], byte j of a row = element 2j in the HIGH nibble, element 2j+1 in the low one; absmax: fp32 [N, K/64].
+ *   value   W'[n, k] = bf16_rne(fl32(code[q] * absmax)).  A quantised linear layer IS the bf16 linear layer on W': dwm_gemm_nf4
+ *           feeds the matrix pipes exactly these bits (the weights are scaled and rounded BEFORE the product; nothing is scaled
+ *           after it) and accumulates in fp32 like dwm_gemm_bf16.
+ * Not built: double quantisation (quantised absmax), fp4, 8-bit weights.  Files written by `bitsandbytes` are not a
+ * compatibility target: the package is not part of this stack, so agreement with it could not be checked.
+ *
+ * Errors, all three: null pointers, sizes <= 0, K % 64 != 0, a leading dimension below its row length: DWM_EINVAL; sizes past the
+ * index range: DWM_EUNSUPPORTED; w / q / A / bias / C / C32 off 16 bytes, absmax / code off 4 bytes, a leading dimension that is
+ * not a multiple of 16 bytes: DWM_EALIGN.  Deterministic; the library reads no environment for them.
+ *
+ * dwm_nf4_quantize: w bf16 [N, K] (row stride ldw elements) -> q, absmax (both contiguous).  Runs once per weight at load time. */
+int dwm_nf4_quantize(const void* w_bf16, int64_t ldw, int64_t N, int64_t K, const float* code, uint8_t* q, float* absmax,
+                     void* stream);
+/* q, absmax -> W' bf16 [N, K] (row stride ldw) */
+int dwm_nf4_dequantize(const uint8_t* q, const float* absmax, int64_t N, int64_t K, const float* code, void* w_bf16, int64_t ldw,
+                       void* stream);
+
+/* out = A[M, K] W'^T (+ bias).  A: bf16, row stride lda; bias: bf16 [N] or NULL.  EXACTLY ONE of the two outputs is given (else
+ * DWM_EINVAL): C, bf16 [M, N] with ldc, receives bf16(acc + bias); C32, the fp32 residual stream [M, N] with ldc32, is UPDATED IN
+ * PLACE, C32 += acc + bias (what the RESID launches of dwm_gemm_bf16 do to it in the encoders).  K % 64 == 0; N % 8 == 0 (else
+ * DWM_EUNSUPPORTED); any M >= 1.  One fixed K order, no split-K and no choice taken from M: a row's result does not depend on
+ * how many rows the launch has. */
+typedef struct dwm_gemm_nf4_args {
+    const void* A; int64_t lda;
+    const uint8_t* q; const float* absmax; const float* code;
+    const void* bias;
+    void* C; int64_t ldc;
+    float* C32; int64_t ldc32;
+    int64_t M, N, K;
+} dwm_gemm_nf4_args;
+int dwm_gemm_nf4(const dwm_gemm_nf4_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

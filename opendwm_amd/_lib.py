@@ -131,6 +131,11 @@ class TextAttnArgs(C.Structure):
                 ("heads", _i32), ("scale", _f32), ("causal", _i32), ("bias", _vp)]
 
 
+class GemmNf4Args(C.Structure):
+    _fields_ = [("A", _vp), ("lda", _i64), ("q", _vp), ("absmax", _vp), ("code", _vp), ("bias", _vp), ("C", _vp), ("ldc", _i64),
+                ("C32", _vp), ("ldc32", _i64), ("M", _i64), ("N", _i64), ("K", _i64)]
+
+
 # name -> (restype, argtypes); every symbol include/dwm_hip.h declares
 SIGNATURES = {
     "dwm_abi_version": (_i32, []),
@@ -239,6 +244,10 @@ SIGNATURES = {
     "dwm_rmsnorm_rows": (_i32, [_vp, _i64, _i64, _i64, _vp, _f32, _vp, _i64, _vp]),
     "dwm_text_embed": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "dwm_text_act": (_i32, [_vp, _i64, _i64, _i64, _i32, _i32, _vp, _i64, _vp]),
+    # NF4 4-bit weights
+    "dwm_nf4_quantize": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "dwm_nf4_dequantize": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "dwm_gemm_nf4": (_i32, [C.POINTER(GemmNf4Args), _vp]),
 }
 
 _ERR = {-1: "DWM_EINVAL (bad shape / null pointer)", -2: "DWM_EALIGN (alignment)",

@@ -1386,6 +1386,92 @@ def text_act(x: torch.Tensor, kind: str, gated: bool = False, out: Optional[torc
     return out
 
 
+# -------------------------------------------------------------------- NF4 4-bit weights
+def _nf4_operands(q: torch.Tensor, absmax: torch.Tensor, what: str):
+    """checks of a packed weight (nf4.py): q uint8 [N, K/2], absmax fp32 [N, K/64], both contiguous on one device -> (N, K)"""
+    from . import nf4
+    for name, t, dt in (("q", q, torch.uint8), ("absmax", absmax, f32)):
+        if not t.is_cuda or t.dtype != dt or t.dim() != 2 or not t.is_contiguous():
+            raise RuntimeError(f"{what}: {name} must be a contiguous 2-D {dt} device tensor")
+    N, K = q.shape[0], 2 * q.shape[1]
+    if N == 0 or K == 0 or K % nf4.BLOCK != 0 or tuple(absmax.shape) != (N, K // nf4.BLOCK) or absmax.device != q.device:
+        raise RuntimeError(f"{what}: q {tuple(q.shape)} and absmax {tuple(absmax.shape)} are not [N, K/2] and [N, K/{nf4.BLOCK}] of one weight")
+    if q.data_ptr() % 16 != 0 or absmax.data_ptr() % 4 != 0:
+        raise RuntimeError(f"{what}: q must be 16-byte aligned, absmax 4-byte aligned")
+    return N, K
+
+
+def _chk_aligned(t: torch.Tensor, name: str):
+    es = t.element_size()
+    if t.data_ptr() % 16 != 0 or (t.stride(0) * es) % 16 != 0:
+        raise RuntimeError(f"{name}: data pointer and row stride must be multiples of 16 bytes")
+
+
+def nf4_quantize(w: torch.Tensor):
+    """bf16 [N, K] (contiguous rows, K % 64 == 0) -> (q uint8 [N, K/2], absmax fp32 [N, K/64]) by dwm_nf4_quantize"""
+    from . import nf4
+    _chk2d(w, "w")
+    _chk_aligned(w, "w")
+    N, K = w.shape
+    if N == 0 or K == 0 or K % nf4.BLOCK != 0:
+        raise RuntimeError(f"nf4_quantize: K = {K} must be a positive multiple of {nf4.BLOCK} (and N = {N} positive)")
+    q = torch.empty((N, K // 2), dtype=torch.uint8, device=w.device)
+    absmax = torch.empty((N, K // nf4.BLOCK), dtype=f32, device=w.device)
+    _call("dwm_nf4_quantize", w.data_ptr(), w.stride(0), N, K, nf4.device_code(w.device).data_ptr(), q.data_ptr(), absmax.data_ptr())
+    return q, absmax
+
+
+def nf4_dequantize(q: torch.Tensor, absmax: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """W' = bf16(code[q] * absmax), bf16 [N, K] (dwm_nf4_dequantize); out: contiguous rows, any 16-byte-aligned row stride"""
+    from . import nf4
+    N, K = _nf4_operands(q, absmax, "nf4_dequantize")
+    if out is None:
+        out = torch.empty((N, K), dtype=bf16, device=q.device)
+    _chk2d(out, "out")
+    _chk_aligned(out, "out")
+    if tuple(out.shape) != (N, K) or out.device != q.device:
+        raise RuntimeError(f"nf4_dequantize: out must be [{N}, {K}] on the device of q, got {tuple(out.shape)}")
+    _call("dwm_nf4_dequantize", q.data_ptr(), absmax.data_ptr(), N, K, nf4.device_code(q.device).data_ptr(), out.data_ptr(), out.stride(0))
+    return out
+
+
+def gemm_nf4(a: torch.Tensor, q: torch.Tensor, absmax: torch.Tensor, bias: Optional[torch.Tensor] = None, *,
+             out: Optional[torch.Tensor] = None, out32: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """a [M, K] bf16 times the NF4 weight (q, absmax) [N, K] transposed, plus bias (dwm_gemm_nf4): the bf16 linear layer on the
+    dequantised weight W', the weight dequantised on the way into the matrix pipes.  Returns bf16 [M, N] (`out`, allocated if
+    neither output is given) or, with `out32` (fp32 [M, N], the residual stream), adds the result into it in place and returns
+    it.  N % 8 == 0.  A row's result does not depend on M."""
+    from . import nf4
+    _chk2d(a, "a")
+    _chk_aligned(a, "a")
+    N, K = _nf4_operands(q, absmax, "gemm_nf4")
+    M = a.shape[0]
+    if M == 0 or a.shape[1] != K or a.device != q.device:
+        raise RuntimeError(f"gemm_nf4: a must be [M >= 1, {K}] on the device of q, got {tuple(a.shape)}")
+    if N % 8 != 0:
+        raise NotImplementedError(f"gemm_nf4: N = {N} must be a multiple of 8")
+    _chkvec(bias, "bias")
+    if bias is not None and (bias.numel() != N or bias.device != a.device or bias.data_ptr() % 16 != 0):
+        raise RuntimeError(f"gemm_nf4: bias must be a 16-byte-aligned vector of {N} elements on the device of a")
+    if out is not None and out32 is not None:
+        raise RuntimeError("gemm_nf4: give out or out32, not both")
+    if out32 is None and out is None:
+        out = torch.empty((M, N), dtype=bf16, device=a.device)
+    res = out if out32 is None else out32
+    _chk2d(res, "out" if out32 is None else "out32", bf16 if out32 is None else f32)
+    _chk_aligned(res, "out" if out32 is None else "out32")
+    if tuple(res.shape) != (M, N) or res.device != a.device:
+        raise RuntimeError(f"gemm_nf4: the output must be [{M}, {N}] on the device of a, got {tuple(res.shape)}")
+    if _overlaps(res, a):
+        raise RuntimeError("gemm_nf4: the output must not overlap a")
+    g = _lib.GemmNf4Args()
+    g.A, g.lda, g.q, g.absmax, g.code, g.bias = a.data_ptr(), a.stride(0), q.data_ptr(), absmax.data_ptr(), nf4.device_code(a.device).data_ptr(), _p(bias)
+    g.C, g.ldc, g.C32, g.ldc32 = _p(out), (out.stride(0) if out is not None else 0), _p(out32), (out32.stride(0) if out32 is not None else 0)
+    g.M, g.N, g.K = M, N, K
+    _call("dwm_gemm_nf4", C.byref(g))
+    return res
+
+
 def cast_bf16(x: torch.Tensor) -> torch.Tensor:
     if x.dtype == bf16:
         return x

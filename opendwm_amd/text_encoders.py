@@ -22,11 +22,33 @@ another head width, L > 128 or an activation the kernels do not have raise.
 
 TOKENISATION STAYS WITH THE CALLER: the tokenizers are host string code and no vocabulary files ship with this package; every
 entry point here takes token ids (int64 [N, L], normally still on the host, where they are checked against the vocabulary).
-Out of scope: an fp32 accuracy path, training (the encoders are frozen in the reference), L > 128, HIP-graph capture."""
+Out of scope: an fp32 accuracy path, training (the encoders are frozen in the reference), L > 128, HIP-graph capture.
+
+4-BIT WEIGHTS (`quantization_config`): all three classes take the dict the reference's example configs pass as
+`text_encoder_load_args.quantization_config` (the key names of transformers.BitsAndBytesConfig; an object with `to_dict()` is
+accepted too):
+  * `load_in_4bit=True` with `bnb_4bit_quant_type="nf4"` is what is built (opendwm_amd/nf4.py); `bnb_4bit_compute_dtype` is accepted
+    and IGNORED - the compute dtype here is bf16 whatever it says; fp4 (also the default of a config that names no type),
+    `bnb_4bit_use_double_quant=True` and `load_in_8bit=True` raise NotImplementedError in the constructor;
+  * `llm_int8_skip_modules`: name fragments of the linear layers that stay bf16; it REPLACES the default list, as in transformers.
+    Defaults (transformers 4.48): T5 `["wo"]` (its `_keep_in_fp32_modules`), CLIP `["text_projection"]` (the last parameter).
+    Every other nn.Linear of the encoder layers is quantised; embeddings, norms, biases and T5's relative bias table never are;
+  * `route` (a key of this package): "fused" - every quantised layer is ONE ops.gemm_nf4 launch - or "dequant" - ops.nf4_dequantize
+    into one bf16 scratch buffer (sized for the model's largest quantised operand, reused layer by layer in stream order), then
+    the bf16 GEMM with exactly the arguments of the unquantised model.  Default "dequant", the faster one on T5-XXL at 9 rows of
+    77 tokens ("fused" is faster up to ~3 rows, on CLIP up to 12).  Fixed per model, never chosen from the row count, so the
+    dedupe guarantee above holds on both.  A quantised layer IS the bf16 layer on W' = bf16(code[q] * absmax): "dequant" is
+    bit-equal to the unquantised model loaded with W'.
+Quantisation happens where operand packing happens: at the first forward after `load_state_dict` / `.to()`; Q | K | V (and wi_0 |
+wi_1) are packed first and quantised as one operand, then the bf16 storage of every quantised weight is released.  From then on
+`state_dict()` shows `weight_nf4` (uint8 [N, K/2]) and `weight_absmax` (fp32 [N, K/64]) buffers in place of each quantised
+`weight`.  LOADING SUCH A DICT BACK IS NOT BUILT: `load_state_dict` takes the released bf16 checkpoints only and raises a
+RuntimeError that names the `weight_nf4` / `weight_absmax` keys it was given.  `.to()` and `load_state_dict` return the model to
+"bf16, quantisation pending" (`.to()` by dequantising to W', which quantises back to the same codes)."""
 from __future__ import annotations
 
 import math
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 from torch import nn
@@ -86,16 +108,54 @@ def dedupe_rows(ids: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     return distinct, index
 
 
-class _Frozen(nn.Module):
-    """what the three classes share: config, `.device` / `.dtype`, the packed-operand cache and its invalidation"""
+NF4_ROUTES = ("fused", "dequant")
+NF4_DEFAULT_ROUTE = "dequant"        # the faster one on T5-XXL at 9 rows of 77 tokens (14.7 ms against 17.5 ms "fused"): DESIGN.md §24
 
-    def __init__(self, defaults: dict, config: Optional[dict], kw: dict):
+
+def parse_quantization_config(qc, default_skip) -> Optional[dict]:
+    """None, or dict(skip=[name fragments that stay bf16], route=...) from a BitsAndBytesConfig-style dict (see the module
+    docstring).  Runs on the host, in the constructors."""
+    if qc is None:
+        return None
+    qc = dict(qc.to_dict()) if hasattr(qc, "to_dict") else dict(qc)
+    if qc.get("load_in_8bit"):
+        raise NotImplementedError("quantization_config: load_in_8bit is not built (4-bit NF4 only)")
+    if not qc.get("load_in_4bit"):
+        raise ValueError("quantization_config: load_in_4bit=True is the one mode there is (pass quantization_config=None for bf16)")
+    kind = qc.get("bnb_4bit_quant_type", "fp4")                       # BitsAndBytesConfig's own default
+    if kind != "nf4":
+        raise NotImplementedError(f"quantization_config: bnb_4bit_quant_type={kind!r} is not built; only 'nf4' is")
+    if qc.get("bnb_4bit_use_double_quant"):
+        raise NotImplementedError("quantization_config: bnb_4bit_use_double_quant (quantised absmax) is not built")
+    route = qc.get("route", NF4_DEFAULT_ROUTE)
+    if route not in NF4_ROUTES:
+        raise ValueError(f"quantization_config: route must be one of {NF4_ROUTES}, got {route!r}")
+    skip = qc.get("llm_int8_skip_modules")
+    return dict(skip=list(default_skip if skip is None else skip), route=route)
+
+
+class _Nf4Weight:
+    """one quantised GEMM operand: q uint8 [N, K/2], absmax fp32 [N, K/64] (opendwm_amd/nf4.py)"""
+
+    def __init__(self, q: torch.Tensor, absmax: torch.Tensor):
+        self.q, self.absmax = q, absmax
+        self.shape = (q.shape[0], 2 * q.shape[1])
+        self.numel = self.shape[0] * self.shape[1]
+
+
+class _Frozen(nn.Module):
+    """what the three classes share: config, `.device` / `.dtype`, the packed-operand cache and its invalidation, 4-bit weights"""
+    NF4_DEFAULT_SKIP: Tuple[str, ...] = ()
+
+    def __init__(self, defaults: dict, config: Optional[dict], kw: dict, quantization_config=None):
         super().__init__()
         cfg = dict(defaults)
         cfg.update(dict(config or {}))
         cfg.update(kw)
         self.config = cfg
         self._packed: Optional[dict] = None
+        self.quantization = parse_quantization_config(quantization_config, self.NF4_DEFAULT_SKIP)
+        self._quantised: List[nn.Module] = []            # the nn.Linear modules whose bf16 weight is released
 
     @property
     def device(self):
@@ -107,11 +167,85 @@ class _Frozen(nn.Module):
 
     def _apply(self, fn, *a, **k):          # .to() / .cuda() copy every parameter on its own: the packed views are gone
         self._packed = None
+        self._unquantise(materialise=True)
         return super()._apply(fn, *a, **k)
 
     def load_state_dict(self, state_dict, *a, **k):
+        packed = sorted(key for key in state_dict if key.endswith((".weight_nf4", ".weight_absmax")))
+        if packed:
+            raise RuntimeError("load_state_dict: loading the state dict of a quantised model is not built - load the bf16 checkpoint "
+                               f"and let the first forward quantise it; got {packed}")
         self._packed = None
+        self._unquantise(materialise=False)
         return super().load_state_dict(self._checkpoint_keys(dict(state_dict)), *a, **k)
+
+    # ---- 4-bit weights
+    def _linear_groups(self):
+        """tuples of module names, one per GEMM operand: the nn.Linear layers whose weights are stacked into it"""
+        raise NotImplementedError
+
+    def _stays_bf16(self, name: str) -> bool:
+        return any(key == name or (key + ".") in (name + ".") for key in self.quantization["skip"])
+
+    def _wants_nf4(self, names) -> bool:
+        if self.quantization is None:
+            return False
+        stays = [self._stays_bf16(n) for n in names]
+        if any(stays) and not all(stays):
+            raise NotImplementedError(f"llm_int8_skip_modules splits {names}: they are one packed GEMM operand, quantised as a whole or not at all")
+        return not stays[0]
+
+    def quantised_modules(self) -> List[str]:
+        """names of the nn.Linear layers this model's configuration quantises (host side; nothing is computed)"""
+        return [n for names in self._linear_groups() if self._wants_nf4(names) for n in names]
+
+    def _operand(self, names):
+        """the GEMM operand of the layers `names`: their weights stacked into one tensor (several names; the parameters become
+        views of it), as bf16 - or, where the configuration says so, quantised, the bf16 storage released"""
+        mods = [self.get_submodule(n) for n in names]
+        w = self._pack([m.weight for m in mods]) if len(mods) > 1 else mods[0].weight.data
+        if not self._wants_nf4(names):
+            return w
+        q, absmax = ops.nf4_quantize(w.contiguous())
+        r = 0
+        for m in mods:
+            n = m.weight.shape[0]
+            m.weight = None
+            m.register_buffer("weight_nf4", q[r:r + n])
+            m.register_buffer("weight_absmax", absmax[r:r + n])
+            self._quantised.append(m)
+            r += n
+        return _Nf4Weight(q, absmax)
+
+    def _with_scratch(self, packed: dict, operands) -> dict:
+        """the "dequant" route's one bf16 buffer, sized for the largest quantised operand"""
+        sizes = [o.numel for o in operands if isinstance(o, _Nf4Weight)]
+        if sizes and self.quantization["route"] == "dequant":
+            packed["scratch"] = torch.empty(max(sizes), dtype=bf16, device=self.device)
+        return packed
+
+    def _unquantise(self, materialise: bool):
+        """back to "bf16, quantisation pending": every released weight is a bf16 parameter again - holding W' (materialise), or
+        uninitialised storage that load_state_dict is about to fill"""
+        for m in self._quantised:
+            q, absmax = m._buffers.pop("weight_nf4"), m._buffers.pop("weight_absmax")
+            if materialise:
+                w = ops.nf4_dequantize(q, absmax)
+            else:
+                w = torch.empty((q.shape[0], 2 * q.shape[1]), dtype=bf16, device=q.device)
+            m.weight = nn.Parameter(w, requires_grad=False)
+        self._quantised = []
+
+    def _linear(self, x, op, bias=None, h=None):
+        """x op^T (+ bias) -> bf16, or added in place into the fp32 residual stream h (which is returned).  op: a bf16 weight - the
+        launches of the unquantised model - or an _Nf4Weight on the model's route"""
+        if isinstance(op, _Nf4Weight):
+            if self.quantization["route"] == "fused":
+                return ops.gemm_nf4(x, op.q, op.absmax, bias, out32=h)
+            op = ops.nf4_dequantize(op.q, op.absmax, out=self._packed["scratch"][:op.numel].view(op.shape))
+        if h is None:
+            return ops.gemm(x, op, bias, split_k=1)
+        return ops.gemm(x, op, bias, epilogue=EPI_RESID, res=h, out32=h, mirror=False)
 
     def _checkpoint_keys(self, sd):
         return sd
@@ -183,11 +317,13 @@ class _CLIPTextTransformer(nn.Module):
 
 
 class CLIPTextModel(_Frozen):
-    """transformers.CLIPTextModel on the HIP path; `[0]` is last_hidden_state, `[1]` pooler_output"""
+    """transformers.CLIPTextModel on the HIP path; `[0]` is last_hidden_state, `[1]` pooler_output.
+    quantization_config: None (bf16) or the 4-bit NF4 dict of the module docstring"""
     OUTPUT_ORDER = ("last_hidden_state", "pooler_output", "hidden_states")
+    NF4_DEFAULT_SKIP = ("text_projection",)
 
-    def __init__(self, config: Optional[dict] = None, **kw):
-        super().__init__(CLIP_DEFAULTS, config, kw)
+    def __init__(self, config: Optional[dict] = None, quantization_config=None, **kw):
+        super().__init__(CLIP_DEFAULTS, config, kw, quantization_config)
         c = self.config
         if c["hidden_size"] != 64 * c["num_attention_heads"]:
             raise NotImplementedError(f"CLIP head width {c['hidden_size']} / {c['num_attention_heads']} is not 64")
@@ -195,6 +331,15 @@ class CLIPTextModel(_Frozen):
             raise NotImplementedError(f"CLIP activation {c['hidden_act']!r} is not one of {sorted(ops.TEXT_ACT_KINDS)}")
         self.text_model = _CLIPTextTransformer(c)
         self.eval()
+        self.quantised_modules()                    # a skip list that splits a packed operand is refused here
+
+    def _linear_groups(self):
+        for i in range(self.config["num_hidden_layers"]):
+            p = f"text_model.encoder.layers.{i}."
+            yield tuple(p + f"self_attn.{n}_proj" for n in "qkv")
+            yield (p + "self_attn.out_proj",)
+            yield (p + "mlp.fc1",)
+            yield (p + "mlp.fc2",)
 
     def _checkpoint_keys(self, sd):
         sd = {k: v for k, v in sd.items() if not k.endswith("position_ids")}         # a buffer of older checkpoints
@@ -204,12 +349,14 @@ class CLIPTextModel(_Frozen):
 
     def _operands(self):
         if self._packed is None:
+            groups = list(self._linear_groups())
             layers = []
-            for l in self.text_model.encoder.layers:
+            for i, l in enumerate(self.text_model.encoder.layers):
                 a = l.self_attn
-                layers.append((self._pack([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight]),
-                               self._pack([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias])))
-            self._packed = dict(qkv=layers)
+                bqkv = self._pack([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias])
+                layers.append((self._operand(groups[4 * i]), bqkv) + tuple(self._operand(g) for g in groups[4 * i + 1:4 * i + 4]))
+            more = [self._operand(g) for g in groups[4 * len(layers):]]            # text_projection, where there is one
+            self._packed = self._with_scratch(dict(qkv=layers, more=more), [o for l in layers for o in l] + more)
         return self._packed
 
     @torch.no_grad()
@@ -225,14 +372,14 @@ class CLIPTextModel(_Frozen):
         h = ops.text_embed(ids, tm.embeddings.token_embedding.weight, tm.embeddings.position_embedding.weight)
         states = [ops.cast_bf16(h).view(N, L, D)] if output_hidden_states else None
         ao = torch.empty((N * L, D), dtype=bf16, device=self.device)
-        for l, (wqkv, bqkv) in zip(tm.encoder.layers, self._operands()["qkv"]):
+        for l, (wqkv, bqkv, wout, wfc1, wfc2) in zip(tm.encoder.layers, self._operands()["qkv"]):
             y = ops.layernorm(h, eps=eps, weight=l.layer_norm1.weight, bias=l.layer_norm1.bias, x32=True)
-            qkv = ops.gemm(y, wqkv, bqkv, split_k=1)
+            qkv = self._linear(y, wqkv, bqkv)
             ops.text_attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], ao, N, L, H, 0.125, causal=True)
-            ops.gemm(ao, l.self_attn.out_proj.weight, l.self_attn.out_proj.bias, epilogue=EPI_RESID, res=h, out32=h, mirror=False)
+            self._linear(ao, wout, l.self_attn.out_proj.bias, h)
             y = ops.layernorm(h, eps=eps, weight=l.layer_norm2.weight, bias=l.layer_norm2.bias, x32=True, out=y)
-            f = ops.text_act(ops.gemm(y, l.mlp.fc1.weight, l.mlp.fc1.bias, split_k=1), c["hidden_act"])
-            ops.gemm(f, l.mlp.fc2.weight, l.mlp.fc2.bias, epilogue=EPI_RESID, res=h, out32=h, mirror=False)
+            f = ops.text_act(self._linear(y, wfc1, l.mlp.fc1.bias), c["hidden_act"])
+            self._linear(f, wfc2, l.mlp.fc2.bias, h)
             if output_hidden_states:
                 states.append(ops.cast_bf16(h).view(N, L, D))
         last = ops.layernorm(h, eps=eps, weight=tm.final_layer_norm.weight, bias=tm.final_layer_norm.bias, x32=True)
@@ -248,11 +395,15 @@ class CLIPTextModelWithProjection(CLIPTextModel):
     """transformers.CLIPTextModelWithProjection: `[0]` is text_embeds = text_projection(pooled) (ctsd.py:792 relies on it)"""
     OUTPUT_ORDER = ("text_embeds", "last_hidden_state", "hidden_states")
 
-    def __init__(self, config: Optional[dict] = None, **kw):
-        super().__init__(config, **kw)
+    def __init__(self, config: Optional[dict] = None, quantization_config=None, **kw):
+        super().__init__(config, quantization_config, **kw)
         if self.config["projection_dim"] % 8:
             raise NotImplementedError("projection_dim must be a multiple of 8")
         self.text_projection = nn.Linear(self.config["hidden_size"], self.config["projection_dim"], bias=False)
+
+    def _linear_groups(self):
+        yield from super()._linear_groups()
+        yield ("text_projection",)
 
     def _checkpoint_keys(self, sd):
         proj = {k: v for k, v in sd.items() if k.startswith("text_projection.")}
@@ -261,7 +412,7 @@ class CLIPTextModelWithProjection(CLIPTextModel):
 
     def forward(self, input_ids, output_hidden_states: bool = False, **unused):
         last, pooled, states = self._encode(input_ids, output_hidden_states)
-        embeds = ops.gemm(pooled, self.text_projection.weight, split_k=1)
+        embeds = self._linear(pooled, self._operands()["more"][0])
         return TextEncoderOutput(self.OUTPUT_ORDER, text_embeds=embeds, last_hidden_state=last, hidden_states=states, pooler_output=pooled)
 
 
@@ -321,9 +472,10 @@ class _T5Stack(nn.Module):
 class T5EncoderModel(_Frozen):
     """transformers.T5EncoderModel on the HIP path (the gated-GELU encoders: T5 v1.1, T5-XXL); `[0]` is last_hidden_state"""
     OUTPUT_ORDER = ("last_hidden_state", "hidden_states")
+    NF4_DEFAULT_SKIP = ("wo",)
 
-    def __init__(self, config: Optional[dict] = None, **kw):
-        super().__init__(T5_DEFAULTS, config, kw)
+    def __init__(self, config: Optional[dict] = None, quantization_config=None, **kw):
+        super().__init__(T5_DEFAULTS, config, kw, quantization_config)
         c = self.config
         if c["d_kv"] != 64:
             raise NotImplementedError(f"T5 head width d_kv = {c['d_kv']} is not 64")
@@ -336,6 +488,15 @@ class T5EncoderModel(_Frozen):
         self.encoder = _T5Stack(c, self.shared)
         self._bias: Dict[int, torch.Tensor] = {}
         self.eval()
+        self.quantised_modules()
+
+    def _linear_groups(self):
+        for i in range(self.config["num_layers"]):
+            a, d = f"encoder.block.{i}.layer.0.SelfAttention.", f"encoder.block.{i}.layer.1.DenseReluDense."
+            yield (a + "q", a + "k", a + "v")
+            yield (a + "o",)
+            yield (d + "wi_0", d + "wi_1")
+            yield (d + "wo",)
 
     def _apply(self, fn, *a, **k):
         self._bias = {}
@@ -360,11 +521,9 @@ class T5EncoderModel(_Frozen):
 
     def _operands(self):
         if self._packed is None:
-            blocks = []
-            for b in self.encoder.block:
-                a, d = b.layer[0].SelfAttention, b.layer[1].DenseReluDense
-                blocks.append((self._pack([a.q.weight, a.k.weight, a.v.weight]), self._pack([d.wi_0.weight, d.wi_1.weight])))
-            self._packed = dict(blocks=blocks)
+            groups = list(self._linear_groups())
+            blocks = [tuple(self._operand(g) for g in groups[4 * i:4 * i + 4]) for i in range(len(self.encoder.block))]
+            self._packed = self._with_scratch(dict(blocks=blocks), [o for b in blocks for o in b])
         return self._packed
 
     @torch.no_grad()
@@ -379,16 +538,16 @@ class T5EncoderModel(_Frozen):
         states = [ops.cast_bf16(h).view(N, L, D)] if output_hidden_states else None
         ao = torch.empty((N * L, inner), dtype=bf16, device=self.device)
         y = torch.empty((N * L, D), dtype=bf16, device=self.device)
-        for i, (b, (wqkv, wi)) in enumerate(zip(self.encoder.block, self._operands()["blocks"])):
+        for i, (b, (wqkv, wo_attn, wi, wo)) in enumerate(zip(self.encoder.block, self._operands()["blocks"])):
             if output_hidden_states and i > 0:
                 states.append(ops.cast_bf16(h).view(N, L, D))
             ops.rmsnorm_rows(h, b.layer[0].layer_norm.weight, eps, out=y)
-            qkv = ops.gemm(y, wqkv, split_k=1)
+            qkv = self._linear(y, wqkv)
             ops.text_attention(qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:], ao, N, L, H, 1.0, bias=bias)
-            ops.gemm(ao, b.layer[0].SelfAttention.o.weight, epilogue=EPI_RESID, res=h, out32=h, mirror=False)
+            self._linear(ao, wo_attn, None, h)
             ops.rmsnorm_rows(h, b.layer[1].layer_norm.weight, eps, out=y)
-            f = ops.text_act(ops.gemm(y, wi, split_k=1), "gelu_new", gated=True)
-            ops.gemm(f, b.layer[1].DenseReluDense.wo.weight, epilogue=EPI_RESID, res=h, out32=h, mirror=False)
+            f = ops.text_act(self._linear(y, wi), "gelu_new", gated=True)
+            self._linear(f, wo, None, h)
         last = ops.rmsnorm_rows(h, self.encoder.final_layer_norm.weight, eps).view(N, L, D)
         if output_hidden_states:
             states.append(last)                                   # as transformers: the last entry is the normed output
