@@ -614,6 +614,25 @@ int dwm_adamw8_multi(const dwm_adamw8_item* items, const int32_t* block_item, co
                      int64_t chunk, const float* code_m, const float* code_v, float lr, float beta1, float beta2, float eps,
                      float weight_decay, float bias_corr1, float bias_corr2, float grad_scale, void* stream);
 
+/* dwm_adamw_multi / dwm_adamw8_multi with the per-step scalars read from DEVICE memory, so that the host can queue an optimizer
+ * step without knowing the clip coefficient or the non-finite flag of the gradients it applies (a train step replayed as a HIP
+ * graph, DESIGN s25).  items, block tables, chunk, code_m / code_v, beta1, beta2, eps and weight_decay: as for the by-value entry
+ * points.
+ *   hyper [>= 3 floats, device]: hyper[0] = lr, hyper[1] = bias_corr1, hyper[2] = bias_corr2.
+ *   cond  [>= 3 floats, device] or NULL: the `out` of dwm_grad_sumsq_multi - cond[1] = grad_scale, cond[2] = the non-finite flag.
+ *         NULL: grad_scale 1, flag 0.
+ * cond[2] != 0: the launch changes NOTHING - parameters, moments, absmax scales and bf16 copies stay as they were.  Otherwise,
+ * given equal scalar values, every output is bit-equal to what dwm_adamw_multi / dwm_adamw8_multi write (the kernels run one body).
+ * Status codes: those of the by-value entry points, except that the bias corrections cannot be checked on the host (the caller
+ * guarantees > 0); hyper NULL: DWM_EINVAL; hyper or cond not 4-byte aligned: DWM_EALIGN.  Both arrays are read by the kernel on
+ * `stream`: whoever fills them does so on that stream, or orders the writes before the launch. */
+int dwm_adamw_multi_dev(const dwm_adamw_item* items, const int32_t* block_item, const int64_t* block_start, int64_t n_blocks,
+                        int64_t chunk, const float* hyper, const float* cond, float beta1, float beta2, float eps,
+                        float weight_decay, void* stream);
+int dwm_adamw8_multi_dev(const dwm_adamw8_item* items, const int32_t* block_item, const int64_t* block_start, int64_t n_blocks,
+                         int64_t chunk, const float* code_m, const float* code_v, const float* hyper, const float* cond,
+                         float beta1, float beta2, float eps, float weight_decay, void* stream);
+
 /* Gradient norm, clip coefficient and non-finite check of a LIST of fp32 gradients in one read (the work of
  * torch.amp.GradScaler.unscale_ + torch.nn.utils.clip_grad_norm_ + the found-inf check of GradScaler.step, ctsd.py:1401-1432).
  * items / block_item / block_start are DEVICE arrays with the meaning they have for dwm_adamw_multi; chunk: a multiple of 1024,

@@ -219,6 +219,8 @@ SIGNATURES = {
     "dwm_quantize_blockwise8": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _vp]),
     "dwm_dequantize_blockwise8": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "dwm_adamw8_multi": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp]),
+    "dwm_adamw_multi_dev": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _vp]),
+    "dwm_adamw8_multi_dev": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _vp]),
     "dwm_grad_sumsq_multi": (_i32, [_vp, _vp, _vp, _i64, _i64, _f32, _f32, _vp, _vp, _vp, _vp]),
     "dwm_grad_scale_multi": (_i32, [_vp, _vp, _vp, _i64, _i64, _f32, _vp]),
     "dwm_block_permute": (_i32, [C.POINTER(BlockPermuteArgs), _vp]),

@@ -610,13 +610,10 @@ adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restri
 
 // The same update for MANY tensors in one launch: block b works on elements [block_start[b], block_start[b] + chunk) of tensor
 // block_item[b] (a model has 1.4-1.7 k parameter tensors: per-tensor launches made the optimizer step launch-bound).
-__global__ void __launch_bounds__(256)
-adamw_multi_kernel(const dwm_adamw_item* __restrict__ items, const int32_t* __restrict__ block_item,
-                   const int64_t* __restrict__ block_start, int64_t chunk, float lr, float b1, float b2, float eps, float wd,
-                   float bc1, float bc2, float gscale) {
+DWM_DEVINL void adamw_multi_body(const dwm_adamw_item* __restrict__ items, const int32_t* __restrict__ block_item,
+                                 const int64_t* __restrict__ block_start, int64_t chunk, const AdamwHyper& h) {
     int64_t i0, i1;
     const dwm_adamw_item it = dwm_list_chunk(items, block_item, block_start, chunk, i0, i1);
-    const AdamwHyper h{lr, b1, b2, eps, wd, bc1, bc2, gscale};
     float* __restrict__ p = it.p;
     const float* __restrict__ g = it.g;
     float* __restrict__ m = it.m;
@@ -629,6 +626,33 @@ adamw_multi_kernel(const dwm_adamw_item* __restrict__ items, const int32_t* __re
         p[i] = pi; m[i] = mi; v[i] = vi;
         if (pb) pb[i] = f32_to_bf16(pi);
     }
+}
+
+__global__ void __launch_bounds__(256)
+adamw_multi_kernel(const dwm_adamw_item* __restrict__ items, const int32_t* __restrict__ block_item,
+                   const int64_t* __restrict__ block_start, int64_t chunk, float lr, float b1, float b2, float eps, float wd,
+                   float bc1, float bc2, float gscale) {
+    adamw_multi_body(items, block_item, block_start, chunk, AdamwHyper{lr, b1, b2, eps, wd, bc1, bc2, gscale});
+}
+
+// The per-step scalars from DEVICE memory (dwm_adamw_multi_dev / dwm_adamw8_multi_dev): hyper = [lr, bias_corr1, bias_corr2, _],
+// cond = the out of dwm_grad_sumsq_multi [norm, coef, found, _] or null (coef 1, found 0).  Nobody on the host has to know the
+// clip coefficient or the non-finite flag before the launch; a launch whose flag is set returns before its first store.  Every
+// lane reads the same few floats (one scalar load each), then runs the body of the by-value kernel on the same values.
+DWM_DEVINL bool adamw_dev_hyper(const float* __restrict__ hyper, const float* __restrict__ cond, float b1, float b2, float eps,
+                                float wd, AdamwHyper& h) {
+    if (cond && cond[2] != 0.f) return false;
+    h = AdamwHyper{hyper[0], b1, b2, eps, wd, hyper[1], hyper[2], cond ? cond[1] : 1.f};
+    return true;
+}
+
+__global__ void __launch_bounds__(256)
+adamw_multi_dev_kernel(const dwm_adamw_item* __restrict__ items, const int32_t* __restrict__ block_item,
+                       const int64_t* __restrict__ block_start, int64_t chunk, const float* __restrict__ hyper,
+                       const float* __restrict__ cond, float b1, float b2, float eps, float wd) {
+    AdamwHyper h;
+    if (!adamw_dev_hyper(hyper, cond, b1, b2, eps, wd, h)) return;
+    adamw_multi_body(items, block_item, block_start, chunk, h);
 }
 
 // ---------------------------------------------------------------------------------- block-wise 8-bit optimizer state
@@ -757,18 +781,15 @@ dequantize_blockwise8_kernel(const uint8_t* __restrict__ q, const float* __restr
 // adamw_multi_kernel with both moments in the 8-bit format: decode, the same update, re-encode, in one pass (18 bytes per
 // parameter instead of 30).  The parameter update uses the fresh fp32 moments; quantisation only affects what the next step
 // starts from.  Wave w of a workgroup takes blocks w, w + 4, ... of the workgroup's chunk (a multiple of 256 elements).
-__global__ void __launch_bounds__(256)
-adamw8_multi_kernel(const dwm_adamw8_item* __restrict__ items, const int32_t* __restrict__ block_item,
-                    const int64_t* __restrict__ block_start, int64_t chunk, const float* __restrict__ code_m,
-                    const float* __restrict__ code_v, float lr, float b1, float b2, float eps, float wd,
-                    float bc1, float bc2, float gscale) {
+DWM_DEVINL void adamw8_multi_body(const dwm_adamw8_item* __restrict__ items, const int32_t* __restrict__ block_item,
+                                  const int64_t* __restrict__ block_start, int64_t chunk, const float* __restrict__ code_m,
+                                  const float* __restrict__ code_v, const AdamwHyper& h) {
     __shared__ float tab_m[512], tab_v[512];
     q8_stage_table(code_m, tab_m);
     q8_stage_table(code_v, tab_v);
     __syncthreads();
     int64_t i0, i1;
     const dwm_adamw8_item it = dwm_list_chunk(items, block_item, block_start, chunk, i0, i1);
-    const AdamwHyper h{lr, b1, b2, eps, wd, bc1, bc2, gscale};
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* __restrict__ p = it.p;
     const float* __restrict__ g = it.g;
@@ -809,6 +830,25 @@ adamw8_multi_kernel(const dwm_adamw8_item* __restrict__ items, const int32_t* __
         q8_store4c(vq, e, it.n, full, q8_encode4(tab_v, vi, av, zv, true));
         if (lane == 0) { it.m_absmax[blk] = am; it.v_absmax[blk] = av; }
     }
+}
+
+__global__ void __launch_bounds__(256)
+adamw8_multi_kernel(const dwm_adamw8_item* __restrict__ items, const int32_t* __restrict__ block_item,
+                    const int64_t* __restrict__ block_start, int64_t chunk, const float* __restrict__ code_m,
+                    const float* __restrict__ code_v, float lr, float b1, float b2, float eps, float wd,
+                    float bc1, float bc2, float gscale) {
+    adamw8_multi_body(items, block_item, block_start, chunk, code_m, code_v, AdamwHyper{lr, b1, b2, eps, wd, bc1, bc2, gscale});
+}
+
+// (the flag is uniform over the launch: every thread of a skipped launch leaves before the first barrier of the body)
+__global__ void __launch_bounds__(256)
+adamw8_multi_dev_kernel(const dwm_adamw8_item* __restrict__ items, const int32_t* __restrict__ block_item,
+                        const int64_t* __restrict__ block_start, int64_t chunk, const float* __restrict__ code_m,
+                        const float* __restrict__ code_v, const float* __restrict__ hyper, const float* __restrict__ cond,
+                        float b1, float b2, float eps, float wd) {
+    AdamwHyper h;
+    if (!adamw_dev_hyper(hyper, cond, b1, b2, eps, wd, h)) return;
+    adamw8_multi_body(items, block_item, block_start, chunk, code_m, code_v, h);
 }
 
 __global__ void __launch_bounds__(256)
@@ -1149,6 +1189,22 @@ extern "C" int dwm_adamw_multi(const dwm_adamw_item* items, const int32_t* block
     return dwm_launch_status();
 }
 
+static int adamw_dev_operands(const float* hyper, const float* cond) {
+    if (!hyper) return DWM_EINVAL;
+    if ((((uintptr_t)hyper) & 3u) != 0 || (((uintptr_t)cond) & 3u) != 0) return DWM_EALIGN;
+    return DWM_OK;
+}
+
+extern "C" int dwm_adamw_multi_dev(const dwm_adamw_item* items, const int32_t* block_item, const int64_t* block_start,
+                                   int64_t n_blocks, int64_t chunk, const float* hyper, const float* cond, float beta1, float beta2,
+                                   float eps, float weight_decay, void* stream) {
+    if (dwm_bad_list_tables(items, block_item, block_start, n_blocks, chunk)) return DWM_EINVAL;
+    if (const int rc = adamw_dev_operands(hyper, cond)) return rc;
+    hipLaunchKernelGGL(adamw_multi_dev_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, items, block_item,
+                       block_start, chunk, hyper, cond, beta1, beta2, eps, weight_decay);
+    return dwm_launch_status();
+}
+
 extern "C" int dwm_quantize_blockwise8(const float* x, int64_t n, const float* code, int32_t floor_positive, uint8_t* q,
                                        float* absmax, void* stream) {
     if (!x || !code || !q || !absmax || n <= 0) return DWM_EINVAL;
@@ -1173,6 +1229,17 @@ extern "C" int dwm_adamw8_multi(const dwm_adamw8_item* items, const int32_t* blo
         bias_corr1 <= 0.f || bias_corr2 <= 0.f) return DWM_EINVAL;
     hipLaunchKernelGGL(adamw8_multi_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, items, block_item,
                        block_start, chunk, code_m, code_v, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale);
+    return dwm_launch_status();
+}
+
+extern "C" int dwm_adamw8_multi_dev(const dwm_adamw8_item* items, const int32_t* block_item, const int64_t* block_start,
+                                    int64_t n_blocks, int64_t chunk, const float* code_m, const float* code_v, const float* hyper,
+                                    const float* cond, float beta1, float beta2, float eps, float weight_decay, void* stream) {
+    if (dwm_bad_list_tables(items, block_item, block_start, n_blocks, chunk) || !code_m || !code_v || chunk % Q8_BLOCK != 0)
+        return DWM_EINVAL;
+    if (const int rc = adamw_dev_operands(hyper, cond)) return rc;
+    hipLaunchKernelGGL(adamw8_multi_dev_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, items, block_item,
+                       block_start, chunk, code_m, code_v, hyper, cond, beta1, beta2, eps, weight_decay);
     return dwm_launch_status();
 }
 

@@ -100,11 +100,12 @@ class PaddedGrid:
         self.fill_stride2(m)
         m.origin = 0
 
-    def interior_index(self) -> torch.Tensor:
-        """[pixels] int64 padded-row index of every compact pixel (host reference of the kernel's map)"""
-        i = torch.arange(self.I)[:, None, None]
-        y = torch.arange(self.h)[None, :, None]
-        x = torch.arange(self.w)[None, None, :]
+    def interior_index(self, device=None) -> torch.Tensor:
+        """[pixels] int64 padded-row index of every compact pixel (host reference of the kernel's map).  device: where the index is
+        made - the training backwards make it on the GPU, so that they hold no host-to-device copy (a captured train step)"""
+        i = torch.arange(self.I, device=device)[:, None, None]
+        y = torch.arange(self.h, device=device)[None, :, None]
+        x = torch.arange(self.w, device=device)[None, None, :]
         return (i * (self.h + 2) * (self.w + 2) + (y + 1) * (self.w + 2) + x + 1).reshape(-1)
 
 

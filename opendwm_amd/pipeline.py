@@ -512,7 +512,8 @@ class CTSDTrainer:
                  ddp_kwargs: Optional[dict] = None, common_config: Optional[dict] = None, training_config: Optional[dict] = None,
                  reference_latent_count=0, lr_scheduler=None, ddp_comm_dtype: Optional[torch.dtype] = None,
                  train_scheduler=None, optimizer_bits: int = 32, grad_conditioning: str = "torch",
-                 activations: str = "recompute", activation_budget_gib: Optional[float] = None, deterministic: bool = False):
+                 activations: str = "recompute", activation_budget_gib: Optional[float] = None, deterministic: bool = False,
+                 graph: bool = False):
         """common_config["frame_prediction_style"] (None | "diffusion_forcing" | "ctsd") and training_config select the
         training task mix of `make_input_for_prediction`; with "diffusion_forcing" every frame draws its own timestep
         (ctsd.py:1232-1237).  optimizer_bits: 32 = train.AdamW (fp32 moments), 8 = train.AdamW8bit (block-wise 8-bit moments: the
@@ -535,7 +536,16 @@ class CTSDTrainer:
         norm-weight / d(alpha) sums) run their ordered form (ops.ordered_reductions): loss, gradients, parameters and
         optimizer state of a step are then a function of the inputs and the library build only - bit-equal from run to run, between
         "keep" and "recompute", and under a one-rank DDP wrap - for 1.2 % of step time at config 4.  False (default): the atomics, as
-        before.  Multi-rank all-reduce order is RCCL's and not covered."""
+        before.  Multi-rank all-reduce order is RCCL's and not covered.
+        graph (MMDiT and UNet, one GPU): True = after `graph_warmup` (1) eager steps a train_step is host-side staging
+        (the draws and the task mixer, as before), a replay of ONE HIP graph that holds forward, loss, loss scaling and backward, and
+        an optimizer step that is queued without a host read (`dwm_adamw_multi_dev` / `dwm_adamw8_multi_dev`); the loss returned is
+        a copy of the graph's loss buffer.  The clip coefficient and the non-finite flag stay on the device; the host reads them one
+        step late, so `last_grad_norm` and `skipped_steps` lag by one step (`graph_sync()` brings them up to date).
+        `graph_captures` / `graph_replays` count.  The graph is captured again when the keys, shapes or dtypes of the inputs change
+        or the parameters' compute copies were replaced (a state-dict load, `.to()`); a forward of the model outside the trainer
+        needs no recapture.  ValueError with ddp=True, with a clip or a scaler under grad_conditioning="torch", and for a model
+        that is not on the device.  False (default): every launch as before."""
         from . import train as _train
         from .unet import UNetCrossviewTemporalConditionModel
         if activations not in _train.ACTIVATION_POLICIES:
@@ -556,6 +566,18 @@ class CTSDTrainer:
         if grad_conditioning not in ("torch", "fused"):
             raise ValueError(f"grad_conditioning: 'torch' or 'fused', got {grad_conditioning!r}")
         self.grad_conditioning = grad_conditioning
+        self.graph = bool(graph)
+        if self.graph:
+            tc = training_config or {}
+            if ddp:
+                raise ValueError("CTSDTrainer(graph=True): ddp=True is not captured (the bucketed all-reduce runs on RCCL's own "
+                                 "streams); train one GPU per process without the wrap, or leave graph off")
+            if grad_conditioning != "fused" and (tc.get("max_norm_for_grad_clip", max_grad_norm) is not None
+                                                 or tc.get("enable_grad_scaler", False)):
+                raise ValueError("CTSDTrainer(graph=True): a gradient clip or a grad scaler needs grad_conditioning='fused' - the "
+                                 "'torch' route rewrites the gradients through host-synchronising torch calls")
+            if any(not p.is_cuda for p in model.parameters()):
+                raise ValueError("CTSDTrainer(graph=True): the model is not on the device (a HIP graph holds device launches only)")
         self.last_grad_norm, self.skipped_steps, self._warned_nonfinite = 0.0, 0, False
         self.model = model.train()
         self.wrapper = model
@@ -599,6 +621,9 @@ class CTSDTrainer:
             self.grad_scaler = _train.LossScaler() if grad_conditioning == "fused" else torch.amp.GradScaler(dev_type)
         self.weighting_scheme = weighting_scheme
         self.reference_latent_count = reference_latent_count
+        self.graph_warmup, self.graph_captures, self.graph_replays = 1, 0, 0     # graph_warmup: eager steps before the first capture
+        self._g_eager_done = 0
+        self._graph, self._g_key, self._g_pending, self._g_grads_fresh = None, None, None, True
         # SD 2.1 branch (ctsd.py:1240-1253): the model is the UNet -> DDPM noising, epsilon / v_prediction target
         if self.is_unet and train_scheduler is None:
             from .schedulers import DDPMScheduler
@@ -680,41 +705,47 @@ class CTSDTrainer:
             timesteps = timesteps.unsqueeze(-1).repeat_interleave(latents.shape[timesteps.dim()], -1)
         return noisy, timesteps, target.float(), noise
 
-    def _unet_loss(self, latents, conditions, generator, timesteps, noise) -> torch.Tensor:
-        noisy, timesteps, target, _ = self.make_unet_training_pair(latents, generator, timesteps, noise)
-        noisy, timesteps, extra, reference = make_input_for_prediction(
-            noisy, latents.float(), timesteps, self.training_config, self.common_config, generator, self.reference_latent_count)
-        cond = {k: (v.to(bf16) if torch.is_tensor(v) and v.is_floating_point() and k != "added_time_ids" else v)
-                for k, v in conditions.items()}
-        if extra is not None:
-            cond.update(extra)
-        pred = self.wrapper(noisy.to(bf16), timesteps, **cond)[0][0].float()           # :1358-1360: sd_pred[0] as it is
-        if self.training_config.get("disable_reference_frame_loss", False):          # :1363-1367
-            keep = ~reference.view(*pred.shape[:3], 1, 1, 1).to(pred.device)
-            pred, target = pred * keep, target * keep
-        return torch.nn.functional.mse_loss(pred, target, reduction="mean") * self.loss_coef
-
-    def loss(self, latents: torch.Tensor, conditions: Dict[str, torch.Tensor], generator=None,
-             timestep_indices=None, noise=None) -> torch.Tensor:
+    def _stage_inputs(self, latents, conditions, generator, timestep_indices, noise) -> dict:
+        """the host side of `loss`: the draws, the noising and the task mixer in the reference's order and the condition casts ->
+        what the model forward and the loss read (noisy, timesteps, sig - None for the UNet -, target, reference, cond)"""
         if hasattr(self, "deterministic"):      # this trainer's mode holds for its forwards (trainers may share a model)
             self.model.ordered_reductions = self.deterministic
+        sig = None
         if getattr(self, "is_unet", False):
-            return self._unet_loss(latents, conditions, generator, timestep_indices, noise)
-        noisy, timesteps, sig, _ = self.make_training_pair(latents, generator, timestep_indices, noise)
+            noisy, timesteps, target, _ = self.make_unet_training_pair(latents, generator, timestep_indices, noise)
+        else:
+            noisy, timesteps, sig, _ = self.make_training_pair(latents, generator, timestep_indices, noise)
         noisy, timesteps, extra, reference = make_input_for_prediction(
             noisy, latents.float(), timesteps, self.training_config, self.common_config, generator, self.reference_latent_count)
         cond = {k: (v.to(bf16) if torch.is_tensor(v) and v.is_floating_point() and k != "added_time_ids" else v)
                 for k, v in conditions.items()}
         if extra is not None:
             cond.update(extra)
+        if sig is not None:
+            target = latents.float()
+        return dict(noisy=noisy, timesteps=timesteps, sig=sig, target=target, reference=reference, cond=cond)
+
+    def _loss_of(self, s: dict) -> torch.Tensor:
+        """the device side of `loss`: model forward and the loss on what `_stage_inputs` made"""
+        noisy, timesteps, sig, target, reference, cond = (s[k] for k in ("noisy", "timesteps", "sig", "target", "reference", "cond"))
+        if sig is None:
+            pred = self.wrapper(noisy.to(bf16), timesteps, **cond)[0][0].float()           # :1358-1360: sd_pred[0] as it is
+            if self.training_config.get("disable_reference_frame_loss", False):          # :1363-1367
+                keep = ~reference.view(*pred.shape[:3], 1, 1, 1).to(pred.device)
+                pred, target = pred * keep, target * keep
+            return torch.nn.functional.mse_loss(pred, target, reduction="mean") * self.loss_coef
         if hasattr(self, "activations"):        # this trainer's policy holds for its forwards (trainers may share a model)
             self.model.activation_policy, self.model.activation_budget_gib = self.activations, self.activation_budget_gib
         pred = self.wrapper(noisy.to(bf16), timesteps, **cond)[0][0]
-        x0_hat, target = pred.float() * (-sig) + noisy, latents.float()
+        x0_hat = pred.float() * (-sig) + noisy
         if self.training_config.get("disable_reference_frame_loss", False):          # ctsd.py:1363-1367
             keep = ~reference.view(*x0_hat.shape[:3], 1, 1, 1).to(x0_hat.device)
             x0_hat, target = x0_hat * keep, target * keep
         return torch.nn.functional.mse_loss(x0_hat, target, reduction="mean") * self.loss_coef
+
+    def loss(self, latents: torch.Tensor, conditions: Dict[str, torch.Tensor], generator=None,
+             timestep_indices=None, noise=None) -> torch.Tensor:
+        return self._loss_of(self._stage_inputs(latents, conditions, generator, timestep_indices, noise))
 
     # ---- checkpoint / resume in the reference's on-disk layout (ctsd.py:1134-1155 save_checkpoint, :988-992 and
     # :1093-1096 resume; src/dwm/distributed.py): <output>/checkpoints/<step>.pth = the model's state dict (reference
@@ -765,6 +796,164 @@ class CTSDTrainer:
                 scaler.update(found_inf)
         self.optimizer.zero_grad()
 
+    # ---- whole-step HIP graph.  The captured region is `_loss_of` + backward on static copies of what `_stage_inputs`
+    # makes.  A replay reads three kinds of memory only: allocations of the capture's own pool (activations, gradients, every
+    # packed / transposed / padded operand - the model-level caches are dropped before the capture, so the replay rebuilds them, once
+    # per replay as the eager forward does once per optimizer step), tensors this trainer holds (`_g_in`, `_g_scale`, the parameters
+    # and their bf16 compute copies `_g_shadows`, which AdamW refreshes in place), and the split-K GEMM workspace of the capture
+    # stream (`_g_workspace`).  A forward of the model outside the trainer therefore cannot take anything away from a replay.
+    _graph_streams: dict = {}
+
+    @staticmethod
+    def _graph_signature(staged: dict) -> tuple:
+        def sig(k, v):
+            return (k, tuple(v.shape), v.dtype, str(v.device)) if torch.is_tensor(v) else (k, repr(v))
+        flat = [sig(k, v) for k, v in staged.items() if k != "cond"]
+        return tuple(flat + [sig("cond." + k, v) for k, v in sorted(staged["cond"].items())])
+
+    def _graph_shadows(self) -> list:
+        """the bf16 compute copies AdamW writes in place, as blocks.STORE holds them now (None: none, or one that is re-cast)"""
+        from .blocks import STORE
+        out = []
+        for p in self.model.parameters():
+            hit = STORE._shadow.get(id(p)) if (p.dtype == torch.float32 and p.numel() % 4 == 0 and p.is_contiguous()) else None
+            out.append(None if hit is None else hit[1])
+        return out
+
+    def _graph_drop_model_caches(self) -> None:
+        """every tensor the model keeps between forwards except the parameters' in-place compute copies: the capture re-creates what
+        it needs inside its pool"""
+        from .blocks import STORE
+        for m in self.model.modules():
+            for name, empty in (("_pk", None), ("_cache", {}), ("_wcache", {}), ("_alpha_cache", None), ("_text_ctx", None),
+                                ("_adapter_cache", (None, None)), ("_emb_cache", (None, None, None))):
+                if hasattr(m, name):
+                    setattr(m, name, type(empty)(empty) if isinstance(empty, dict) else empty)
+            if hasattr(m, "_scratch"):
+                m._scratch = type(m._scratch)()
+        for p in self.model.parameters():           # compute copies AdamW does not write: re-cast inside the capture
+            if not (p.dtype == torch.float32 and p.is_cuda and p.numel() % 4 == 0 and p.is_contiguous()):
+                STORE._shadow.pop(id(p), None)
+        STORE.bump(keep_shadows=True)
+
+    def _graph_capture(self, staged: dict, key: tuple, scaler) -> None:
+        import time
+        dev = staged["noisy"].device
+        clone = lambda v: v.clone() if torch.is_tensor(v) else v
+        self._g_in = {k: (clone(v) if k != "cond" else {ck: clone(cv) for ck, cv in v.items()}) for k, v in staged.items()}
+        self._g_scale = torch.ones((), dtype=torch.float32, device=dev)
+        # one capture stream per device for every trainer of the process, and with it ONE split-K workspace (ops keeps one per
+        # stream, for good): made here, outside any graph's pool, and held by every trainer whose graph names it
+        if dev.index not in CTSDTrainer._graph_streams:
+            CTSDTrainer._graph_streams[dev.index] = torch.cuda.Stream(device=dev)
+        self._g_stream = CTSDTrainer._graph_streams[dev.index]
+        with torch.cuda.stream(self._g_stream):
+            self._g_workspace = ops._gemm_workspace(dev)
+        params = list(self.model.parameters())
+        carried = None if self._g_grads_fresh else {id(p): p.grad for p in params if p.grad is not None}
+        for p in params:                             # the capture's backward allocates the gradients in its pool
+            p.grad = None
+        self._graph = self._g_grads = self._g_acc = self._g_loss = None
+        self._graph_drop_model_caches()
+        t0 = time.perf_counter()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=self._g_stream, capture_error_mode="thread_local"):
+            loss = self._loss_of(self._g_in)
+            (loss if scaler is None else loss * self._g_scale).backward()
+            self._g_loss = loss.detach()
+        del loss
+        self.graph_capture_seconds = time.perf_counter() - t0
+        self._graph, self._g_key = graph, key
+        self._g_grads = [(p, p.grad) for p in params if p.grad is not None]
+        self._g_shadows = self._graph_shadows()
+        self._graph_drop_model_caches()              # nothing outside the trainer keeps pointing into the pool
+        self._g_acc = None
+        if self.training_config.get("gradient_accumulation_steps") is not None:
+            # the replay ASSIGNS the micro-step's gradients; the running sum of a cycle lives beside them and is what p.grad is
+            self._g_acc = [torch.zeros_like(g) if carried is None or id(p) not in carried else carried[id(p)].clone()
+                           for p, g in self._g_grads]
+            self._g_grads_fresh = carried is None
+        for p, _ in self._g_grads:
+            p.grad = None
+        self.graph_captures += 1
+
+    def _graph_resolve(self, scaler) -> None:
+        """read the (norm, coef, found) of the last optimizing step, which its kernels already acted on: wait for the copy queued
+        behind them, then the host bookkeeping of the eager fused route"""
+        pend, self._g_pending = self._g_pending, None
+        if pend is None:
+            return
+        host, event = pend
+        event.synchronize()
+        self.last_grad_norm, _, found = host.tolist()[:3]
+        if found != 0.0:
+            self.skipped_steps += 1
+            self.optimizer.undo_step()
+            if scaler is None and not self._warned_nonfinite:
+                import warnings
+                warnings.warn("CTSDTrainer(grad_conditioning='fused'): non-finite gradient without a grad scaler - the optimizer "
+                              "step is skipped (further ones silently; see skipped_steps)")
+                self._warned_nonfinite = True
+        if scaler is not None:
+            scaler.update(found != 0.0)
+
+    def graph_sync(self) -> None:
+        """graph mode: bring `last_grad_norm`, `skipped_steps`, the optimizer's step counts and the loss scale up to date with the
+        last train_step (waits for it); a no-op otherwise"""
+        self._graph_resolve(getattr(self, "grad_scaler", None))
+
+    def _graph_optimizer_step(self, scaler) -> None:
+        from . import train_ops as _T
+        from .train import _fp32_grad
+        if scaler is None and self.max_grad_norm is None:
+            self.optimizer.step(device_operands=(None, None))
+            return
+        gs = [_fp32_grad(p) for p, _ in self._g_grads]
+        inv_scale = 1.0 if scaler is None else 1.0 / scaler.get_scale()
+        cond = _T.grad_sumsq_multi(gs, inv_scale, self.max_grad_norm, reuse_items=True)
+        self.optimizer.step(device_operands=(None, cond))
+        host = torch.empty(4, dtype=torch.float32, pin_memory=True)
+        host.copy_(cond, non_blocking=True)
+        event = torch.cuda.Event()
+        event.record()
+        self._g_pending = (host, event)
+
+    def _graph_train_step(self, staged: dict, key: tuple, should_optimize: bool, scaler) -> torch.Tensor:
+        if scaler is not None:                       # the loss scale of this step depends on the flag of the last one
+            self._graph_resolve(scaler)
+        # (a compute copy that did not exist at the capture is not read by the graph: only the ones it holds are compared)
+        if self._graph is None or key != self._g_key or any(b is not None and a is not b
+                                                            for a, b in zip(self._graph_shadows(), self._g_shadows)):
+            self._graph_resolve(scaler)
+            self._graph_capture(staged, key, scaler)
+        for k, v in staged.items():
+            for kk, vv in (v.items() if k == "cond" else ((k, v),)):
+                dst = self._g_in["cond"][kk] if k == "cond" else self._g_in[kk]
+                if torch.is_tensor(vv):
+                    dst.copy_(vv, non_blocking=True)
+        if scaler is not None:
+            self._g_scale.fill_(scaler.get_scale())
+        self._graph.replay()
+        self.graph_replays += 1
+        loss = self._g_loss.clone()                  # the next replay overwrites the buffer
+        grads = [g for _, g in self._g_grads]
+        if self._g_acc is not None:
+            if self._g_grads_fresh:
+                torch._foreach_copy_(self._g_acc, grads)
+            else:
+                torch._foreach_add_(self._g_acc, grads)
+            self._g_grads_fresh = False
+            grads = self._g_acc
+        for (p, _), g in zip(self._g_grads, grads):  # the gradients are where autograd would have left them
+            p.grad = g
+        self._graph_resolve(scaler)                  # (already done with a scaler) behind the queued graph, before the scalars
+        if should_optimize:
+            self._graph_optimizer_step(scaler)
+            self._g_grads_fresh = True
+            for p, _ in self._g_grads:               # optimizer.zero_grad(): the buffers stay with the trainer
+                p.grad = None
+        return loss
+
     def train_step(self, latents: torch.Tensor, conditions: Dict[str, torch.Tensor], generator=None,
                    timestep_indices=None, noise=None, global_step: Optional[int] = None) -> torch.Tensor:
         """one call of the reference's train_step (ctsd.py:1195-1437); `global_step` defaults to the number of calls so far"""
@@ -772,8 +961,15 @@ class CTSDTrainer:
         gs = self.global_step if global_step is None else global_step
         k = self.training_config.get("gradient_accumulation_steps")
         should_optimize = k is None or (gs + 1) % k == 0                                 # :1401-1404
-        sync = contextlib.nullcontext() if (should_optimize or not self.ddp) else self.wrapper.no_sync()
         scaler = getattr(self, "grad_scaler", None)
+        if getattr(self, "graph", False) and self._g_eager_done >= self.graph_warmup:
+            staged = self._stage_inputs(latents, conditions, generator, timestep_indices, noise)
+            loss = self._graph_train_step(staged, self._graph_signature(staged), should_optimize, scaler)
+            if self.lr_scheduler is not None:
+                self.lr_scheduler.step()
+            self.global_step = gs + 1
+            return loss
+        sync = contextlib.nullcontext() if (should_optimize or not self.ddp) else self.wrapper.no_sync()
         with sync:
             loss = self.loss(latents, conditions, generator, timestep_indices, noise)
             (loss if scaler is None else scaler.scale(loss)).backward()                   # :1401-1404
@@ -790,6 +986,9 @@ class CTSDTrainer:
             else:
                 self.optimizer.step()
             self.optimizer.zero_grad()
+        if getattr(self, "graph", False):            # an eager warm-up step of graph mode
+            self._g_eager_done += 1
+            self._g_grads_fresh = should_optimize
         if self.lr_scheduler is not None:                                                # :1434-1435, every call
             self.lr_scheduler.step()
         self.global_step = gs + 1

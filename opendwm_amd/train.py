@@ -850,7 +850,7 @@ class AdapterFn(torch.autograd.Function):
                 xp = None
             if xp is None:
                 grid = PaddedGrid(I, h, w)
-                idx = grid.interior_index().to(x.device)
+                idx = grid.interior_index(x.device)
                 if blk.in_conv is not None:
                     wi = _bf(blk.in_conv.weight).reshape(blk.in_conv.weight.shape[0], -1)
                     if wi.shape[1] != cur.shape[1]:                               # first block: K padded to 64 by unshuffle_tokens
@@ -1128,10 +1128,18 @@ class AdamW(torch.optim.Optimizer):
         return st
 
     @torch.no_grad()
-    def step(self, closure=None, grad_scale: float = 1.0):
+    def step(self, closure=None, grad_scale: float = 1.0, device_operands: Optional[tuple] = None):
         """the step of `AdamW` and of `AdamW8bit`: a parameter whose `exp_avg` is uint8 goes to the `dwm_adamw8_multi` batch of its
-        step count, every other one to the `dwm_adamw_multi` batch; per group the 8-bit batches are launched first"""
+        step count, every other one to the `dwm_adamw_multi` batch; per group the 8-bit batches are launched first.
+        device_operands = (hyper, cond): the step is queued without a host read (`dwm_adamw_multi_dev` / `dwm_adamw8_multi_dev`).
+        cond: None, or the device tensor `train_ops.grad_sumsq_multi` returned - the kernels take the gradient coefficient and the
+        non-finite flag from it and change nothing when the flag is set; `grad_scale` is not used.  hyper: None - lr and the bias
+        corrections of every batch (the values the by-value route passes) go to the device in ONE asynchronous copy from pinned
+        memory - or a device tensor [>= 3] = (lr, bias_corr1, bias_corr2) used for every batch as it is.  The per-parameter step
+        counts advance as if the step took place; a caller that later reads a set flag undoes that with `undo_step()`."""
         name = type(self).__name__
+        self._last_stepped = []
+        launches = []                           # (wrapper, lists, step, hyper) of the step, launched together at the end
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -1154,6 +1162,7 @@ class AdamW(torch.optim.Optimizer):
                 if len(st) == 0:
                     st = self._init_state(p)
                 st["step"] += 1
+                self._last_stepped.append(p)
                 shadow = STORE.bf(p) if (p.is_cuda and p.numel() % 4 == 0 and p.is_contiguous()) else None
                 if shadow is None:
                     STORE._shadow.pop(id(p), None)      # re-cast on next use
@@ -1170,12 +1179,34 @@ class AdamW(torch.optim.Optimizer):
                     batches[step] = tuple([] for _ in row)
                 for lst, t in zip(batches[step], row):
                     lst.append(t)
-            for step, lists in batches8.items():
-                T.adamw8_multi_(*lists, step=step, **hyper)
-            for step, lists in batches32.items():
-                T.adamw_multi_(*lists, step=step, **hyper)
+            launches += [(T.adamw8_multi_, lists, step, hyper) for step, lists in batches8.items()]
+            launches += [(T.adamw_multi_, lists, step, hyper) for step, lists in batches32.items()]
+        if device_operands is None:
+            for fn, lists, step, hyper in launches:
+                fn(*lists, step=step, **hyper)
+        elif launches:
+            given, cond = device_operands
+            dev = launches[0][1][0][0].device
+            if given is None:                   # one row of (lr, bias_corr1, bias_corr2, 0) per launch, one copy for all of them
+                host = torch.empty((len(launches), 4), dtype=torch.float32, pin_memory=True)
+                for row, (_, _, step, hyper) in zip(host, launches):
+                    T.adamw_hyper(hyper["lr"], hyper["beta1"], hyper["beta2"], step, out=row)
+                rows = host.to(dev, non_blocking=True)
+            for i, (fn, lists, step, hyper) in enumerate(launches):
+                fn(*lists, step=step, **hyper, device_operands=(rows[i] if given is None else given, cond))
         STORE.bump(keep_shadows=True)
         return loss
+
+    def undo_step(self) -> None:
+        """take back the bookkeeping of the last `step(device_operands=...)` whose kernels found the non-finite flag set and left
+        every tensor alone: the step counts go back by one, and a state that step created (zero moments, now step 0) is dropped,
+        as if `step` had not been called"""
+        for p in getattr(self, "_last_stepped", []):
+            st = self.state[p]
+            st["step"] -= 1
+            if float(st["step"]) == 0.0:
+                del self.state[p]
+        self._last_stepped = []
 
 
 class AdamW8bit(AdamW):

@@ -277,9 +277,24 @@ def _block_tables(dev: torch.device, chunk: int, numels: tuple) -> _BlockTables:
     return tab
 
 
-def _items(rows, dev: torch.device) -> torch.Tensor:
-    """equal-length rows of integers (the pointers of one tensor's item struct, its element count last) -> the item array on `dev`"""
-    return torch.tensor(rows, dtype=torch.int64).to(dev, non_blocking=True)
+# (device index, rows) -> item array, least recently used first: the lists of a sync-free optimizer step (gradients, fp32 batch, 8-bit
+# batch) hold the same pointers step after step, and a copy from pageable host memory would make the host wait for the stream
+_ITEMS: dict = {}
+
+
+def _items(rows, dev: torch.device, reuse: bool = False) -> torch.Tensor:
+    """equal-length rows of integers (the pointers of one tensor's item struct, its element count last) -> the item array on `dev`.
+    reuse: the array of an earlier call with the same rows, where there is one (eight are kept)"""
+    if not reuse:
+        return torch.tensor(rows, dtype=torch.int64).to(dev, non_blocking=True)
+    key = (dev.index, tuple(rows))
+    hit = _ITEMS.pop(key, None)
+    if hit is None:
+        while len(_ITEMS) >= 8:
+            _ITEMS.pop(next(iter(_ITEMS)))
+        hit = torch.tensor(rows, dtype=torch.int64).to(dev)
+    _ITEMS[key] = hit
+    return hit
 
 
 def _adamw_scalars(lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, step: int, grad_scale: float) -> tuple:
@@ -296,10 +311,34 @@ def adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, p
           *_adamw_scalars(lr, beta1, beta2, eps, weight_decay, step, grad_scale))
 
 
+def _dev_operands(device_operands, dev: torch.device, what: str) -> tuple:
+    """(hyper, cond) of the *_dev entry points checked: hyper fp32 [>= 3] = (lr, bias_corr1, bias_corr2), cond None or fp32 [>= 3] =
+    the out of grad_sumsq_multi, both contiguous on `dev`"""
+    hyper, cond = device_operands
+    for t, name in ((hyper, "hyper"), (cond, "cond")):
+        if t is None and name == "cond":
+            continue
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < 3 or t.device != dev:
+            raise RuntimeError(f"{what}: device_operands {name} must be a contiguous fp32 tensor of at least 3 elements on the "
+                               "tensors' device")
+    return hyper, cond
+
+
+def adamw_hyper(lr: float, beta1: float, beta2: float, step: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """host tensor [4] = (lr, bias_corr1, bias_corr2, 0) of one optimizer step: the `hyper` array of the *_dev entry points, from the
+    scalars `_adamw_scalars` hands the by-value ones (so a float32 of either holds the same bits)"""
+    sc = _adamw_scalars(lr, beta1, beta2, 0.0, 0.0, step, 1.0)
+    out = torch.empty(4, dtype=torch.float32) if out is None else out
+    out[0], out[1], out[2], out[3] = sc[0], sc[5], sc[6], 0.0
+    return out
+
+
 def adamw_multi_(ps, gs, ms, vs, shadows, *, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, step: int,
-                 grad_scale: float = 1.0) -> None:
+                 grad_scale: float = 1.0, device_operands: Optional[tuple] = None) -> None:
     """dwm_adamw_multi: one launch for the whole list (fp32 contiguous p / g / m / v of equal numel per entry; shadows: bf16 copy or
-    None).  All entries share the hyper-parameters and `step`."""
+    None).  All entries share the hyper-parameters and `step`.
+    device_operands = (hyper, cond): dwm_adamw_multi_dev - lr and the bias corrections are read from `hyper`, the gradient
+    coefficient and the non-finite flag from `cond` (None: 1 and 0); `lr`, `step` and `grad_scale` are then not used."""
     if not ps:
         return
     dev = ps[0].device
@@ -309,8 +348,13 @@ def adamw_multi_(ps, gs, ms, vs, shadows, *, lr: float, beta1: float, beta2: flo
             if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel() or t.device != dev:
                 raise RuntimeError("adamw_multi_: fp32 contiguous tensors of one shape on one device expected")
         rows.append((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), 0 if sh is None else sh.data_ptr(), p.numel()))
-    items = _items(rows, dev)                                                         # [n, 6] = dwm_adamw_item[n]
+    items = _items(rows, dev, reuse=device_operands is not None)                      # [n, 6] = dwm_adamw_item[n]
     tab = _block_tables(dev, ADAMW_CHUNK, tuple(r[-1] for r in rows))
+    if device_operands is not None:
+        hyper, cond = _dev_operands(device_operands, dev, "adamw_multi_")
+        _call("dwm_adamw_multi_dev", _p(items), _p(tab.block_item), _p(tab.block_start), tab.block_item.numel(), ADAMW_CHUNK,
+              _p(hyper), _p(cond), beta1, beta2, eps, weight_decay)
+        return
     _call("dwm_adamw_multi", _p(items), _p(tab.block_item), _p(tab.block_start), tab.block_item.numel(), ADAMW_CHUNK,
           *_adamw_scalars(lr, beta1, beta2, eps, weight_decay, step, grad_scale))
 
@@ -351,9 +395,9 @@ def dequantize_blockwise8(q: torch.Tensor, absmax: torch.Tensor, code: torch.Ten
 
 
 def adamw8_multi_(ps, gs, mqs, mas, vqs, vas, shadows, *, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
-                  step: int, grad_scale: float = 1.0) -> None:
+                  step: int, grad_scale: float = 1.0, device_operands: Optional[tuple] = None) -> None:
     """dwm_adamw8_multi: adamw_multi_ with the moments of every entry in the 8-bit format (mq / vq: uint8 codes, ma / va: fp32
-    block scales); the signed table encodes m, the unsigned one v."""
+    block scales); the signed table encodes m, the unsigned one v.  device_operands: as for adamw_multi_ (dwm_adamw8_multi_dev)."""
     if not ps:
         return
     dev = ps[0].device
@@ -366,15 +410,20 @@ def adamw8_multi_(ps, gs, mqs, mas, vqs, vas, shadows, *, lr: float, beta1: floa
         _chk_q8(vq, va, p.numel(), dev, "adamw8_multi_")
         rows.append((p.data_ptr(), g.data_ptr(), mq.data_ptr(), ma.data_ptr(), vq.data_ptr(), va.data_ptr(),
                      0 if sh is None else sh.data_ptr(), p.numel()))
-    items = _items(rows, dev)                                                         # [n, 8] = dwm_adamw8_item[n]
+    items = _items(rows, dev, reuse=device_operands is not None)                      # [n, 8] = dwm_adamw8_item[n]
     tab = _block_tables(dev, ADAMW_CHUNK, tuple(r[-1] for r in rows))
     code_m, code_v = quant8.device_codes(dev)
+    if device_operands is not None:
+        hyper, cond = _dev_operands(device_operands, dev, "adamw8_multi_")
+        _call("dwm_adamw8_multi_dev", _p(items), _p(tab.block_item), _p(tab.block_start), tab.block_item.numel(), ADAMW_CHUNK,
+              _p(code_m), _p(code_v), _p(hyper), _p(cond), beta1, beta2, eps, weight_decay)
+        return
     _call("dwm_adamw8_multi", _p(items), _p(tab.block_item), _p(tab.block_start), tab.block_item.numel(), ADAMW_CHUNK, _p(code_m),
           _p(code_v), *_adamw_scalars(lr, beta1, beta2, eps, weight_decay, step, grad_scale))
 
 
 # ---- gradient norm / clip coefficient / non-finite check in one read (gradnorm.hip)
-def _grad_items(gs, what: str):
+def _grad_items(gs, what: str, reuse: bool = False):
     """(non-empty entries, their dwm_grad_item rows on the device, block tables) of a gradient list"""
     gs = [g for g in gs if g.numel() > 0]
     if not gs:
@@ -384,14 +433,15 @@ def _grad_items(gs, what: str):
         if g.dtype != torch.float32 or not g.is_contiguous() or g.device != dev or not g.is_cuda or g.data_ptr() % 4:
             raise RuntimeError(f"{what}: fp32 contiguous tensors on one HIP device expected (there is no CPU fallback)")
     rows = [(g.data_ptr(), g.numel()) for g in gs]
-    return gs, _items(rows, dev), _block_tables(dev, GRAD_CHUNK, tuple(r[-1] for r in rows))
+    return gs, _items(rows, dev, reuse), _block_tables(dev, GRAD_CHUNK, tuple(r[-1] for r in rows))
 
 
-def grad_sumsq_multi(gs, pre_scale: float = 1.0, max_norm: Optional[float] = None) -> torch.Tensor:
+def grad_sumsq_multi(gs, pre_scale: float = 1.0, max_norm: Optional[float] = None, reuse_items: bool = False) -> torch.Tensor:
     """dwm_grad_sumsq_multi over a list of fp32 tensors (any 4-byte aligned views): device tensor [4] = (|| pre_scale * g ||_2,
     coef = pre_scale * min(1, max_norm / (norm + 1e-6)), 1.0 if any element is inf / nan else 0.0, 0).  max_norm None or <= 0: no
-    clip, coef = pre_scale.  Empty tensors are dropped; an empty list gives (0, pre_scale, 0, 0) without a launch."""
-    gs, items, tab = _grad_items(gs, "grad_sumsq_multi")
+    clip, coef = pre_scale.  Empty tensors are dropped; an empty list gives (0, pre_scale, 0, 0) without a launch.
+    reuse_items: the item array of an earlier call on the same tensors is used again (no host-to-device copy in a steady step)."""
+    gs, items, tab = _grad_items(gs, "grad_sumsq_multi", reuse_items)
     if not gs:
         return torch.tensor([0.0, pre_scale, 0.0, 0.0], dtype=torch.float32)
     partials, flags = tab.grad_scratch()

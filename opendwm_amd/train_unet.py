@@ -33,7 +33,7 @@ bf16 = torch.bfloat16
 
 # ------------------------------------------------------------------------------------------ convolution helpers
 def _interior(grid: PaddedGrid, dev) -> torch.Tensor:
-    return grid.interior_index().to(dev)
+    return grid.interior_index(dev)
 
 
 def _time_interior(tg: TimeGrid, dev) -> torch.Tensor:
