@@ -40,18 +40,49 @@ class ParamStore:
             raise ValueError("compute dtype must be torch.bfloat16 or torch.float32")
         self.precision = dtype
 
+    def memo(self, owner, tag, key, make, per_step: bool = True):
+        """THE cache of what a module keeps between forwards: `owner._memo[tag] = ((key, step), value)`, valid while `key` - and,
+        with `per_step`, the optimizer step - is unchanged; a miss calls `make()` and replaces the entry of that tag.  Caches that
+        keep both compute precisions side by side carry `precision` in the tag, the others in the key.  per_step=False is for what
+        does not depend on the weights (position tables, scratch grids)."""
+        full = (key, self.step if per_step else None)
+        memo = owner.__dict__.get("_memo")
+        if memo is None:
+            memo = owner.__dict__["_memo"] = {}
+        hit = memo.get(tag)
+        if hit is None or hit[0] != full:
+            hit = memo[tag] = (full, make())
+        return hit[1]
+
+    def peek(self, owner, tag):
+        """the value `memo` holds under `tag` if it is of this optimizer step (or not per step), else None"""
+        hit = owner.__dict__.get("_memo", {}).get(tag)
+        return None if hit is None or hit[0][1] not in (None, self.step) else hit[1]
+
+    def drop(self, owner, tag=None) -> None:
+        """forget one entry of `owner`, or all of them"""
+        if tag is None:
+            owner.__dict__.pop("_memo", None)
+        else:
+            owner.__dict__.get("_memo", {}).pop(tag, None)
+
     def cached(self, owner, make):
         """packed tensors of a module (`make()` -> dict), one entry per compute precision, rebuilt after an optimizer step /
-        state-dict load (`bump`) or when `owner._pk` was reset to None"""
-        slot = getattr(owner, "_pk", None)
-        if not isinstance(slot, dict) or "_by_precision" not in slot:
-            slot = {"_by_precision": {}}
-            owner._pk = slot
-        hit = slot["_by_precision"].get(self.precision)
-        if hit is None or hit[0] != self.step:
-            hit = (self.step, make())
-            slot["_by_precision"][self.precision] = hit
-        return hit[1]
+        state-dict load (`bump`) or `drop`"""
+        return self.memo(owner, ("packed", self.precision), None, make)
+
+    def shadow_of(self, p: torch.Tensor) -> Optional[torch.Tensor]:
+        """the compute copy held for `p` now, or None"""
+        hit = self._shadow.get(id(p))
+        return None if hit is None else hit[1]
+
+    def shadow_ids(self) -> set:
+        """id() of every tensor a compute copy is held for"""
+        return set(self._shadow)
+
+    def forget(self, p: torch.Tensor) -> None:
+        """drop the compute copy of `p`: re-cast on next use"""
+        self._shadow.pop(id(p), None)
 
     def bf(self, t: torch.Tensor) -> torch.Tensor:
         """the compute copy of a parameter: bf16, or fp32 while the fp32 accuracy path runs"""
@@ -72,11 +103,7 @@ class ParamStore:
         hit = self._shadow.get(id(t))
         if hit is None or hit[0] != key:
             d = t.detach()
-            if d.is_cuda and d.dtype == torch.float32 and d.is_contiguous() and d.numel() % 4 == 0:
-                sh = ops.cast_bf16(d)
-            else:
-                sh = d.to(bf16).contiguous()
-            hit = (key, sh)
+            hit = (key, ops.cast_bf16(d) if refreshable(d) else d.to(bf16).contiguous())
             self._shadow[id(t)] = hit
         return hit[1]
 
@@ -98,6 +125,19 @@ class ParamStore:
 
 
 STORE = ParamStore()
+
+
+def refreshable(p: torch.Tensor) -> bool:
+    """is the bf16 compute copy of `p` one the HIP kernels write (ops.cast_bf16) and AdamW refreshes in place?"""
+    return p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.numel() % 4 == 0
+
+
+def drop_caches(model: nn.Module) -> None:
+    """forget everything the modules of `model` keep between forwards (STORE.memo); parameters' compute copies stay"""
+    for m in model.modules():
+        STORE.drop(m)
+
+
 # inference: fold the softmax scale and log2(e) into the q RMSNorm weights (Attention.packed "rms_ps") and tell the attention kernels so
 PRESCALE_Q = True
 # dwm_attn_args.variant bits OR-ed into the inference blocks' attention calls (kernel selection; 0 = the library's choice)
@@ -232,8 +272,6 @@ class Attention(nn.Module):
             if self.has_qk_norm:
                 self.norm_added_q = RMSNorm(dim_head, eps)
                 self.norm_added_k = RMSNorm(dim_head, eps)
-        self._pk = None
-        self._pk_step = -1
 
     def packed(self) -> dict:
         def make():
@@ -381,18 +419,13 @@ class AlphaBlender(nn.Module):
         neither the mix factor (its storage, its version, the optimizer step: the HIP AdamW writes through the raw pointer) nor
         the indicator (the same tensor object at the same version; held here, so its address cannot be reused) changed - the
         UNet asks 54 times per denoise step, five tiny launches each.  A write through `.data` (EMA copy, weight surgery, an
-        optimizer that is not this package's) changes none of those: call `blocks.STORE.bump()` (or the model's
-        `_invalidate_packed()`, which `load_state_dict` / `.to()` do) after it, as for every packed weight copy."""
+        optimizer that is not this package's) changes none of those: call `blocks.STORE.bump()` (or `blocks.drop_caches(model)`,
+        which `load_state_dict` / `.to()` do) after it, as for every packed weight copy."""
         mfp, ind = self.mix_factor, image_only_indicator
         if mfp.is_cuda and torch.cuda.is_current_stream_capturing():
             return self._alpha(ind, batch)      # a captured graph derives alpha from the indicator on every replay, as before
-        key = (mfp.data_ptr(), mfp._version, STORE.step, batch, None if ind is None else ind._version)
-        c = getattr(self, "_alpha_cache", None)
-        if c is not None and c[0] == key and c[1] is ind:
-            return c[2]
-        a = self._alpha(ind, batch)
-        self._alpha_cache = (key, ind, a)
-        return a
+        key = (mfp.data_ptr(), mfp._version, batch, id(ind), None if ind is None else ind._version)
+        return STORE.memo(self, "alpha", key, lambda: (ind, self._alpha(ind, batch)))[1]
 
     def _alpha(self, image_only_indicator: Optional[torch.Tensor], batch: int) -> torch.Tensor:
         mf = self.mix_factor.detach().float()
@@ -425,8 +458,6 @@ class VTSelfAttentionBlock(nn.Module):
                                qk_norm=qk_norm, eps=1e-5)
         self.norm3 = nn.LayerNorm(time_mix_inner_dim)
         self.ff = FeedForward(time_mix_inner_dim, activation_fn="geglu")
-        self._pk = None
-        self._pk_step = -1
 
     def packed(self) -> dict:
         def make():

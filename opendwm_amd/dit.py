@@ -24,8 +24,8 @@ import torch
 from torch import nn
 
 from . import ops
-from .blocks import (AlphaBlender, CombinedTimestepTextProjEmbeddings, JointTransformerBlock,
-                     TimestepEmbedding, VTSelfAttentionBlock, _AdaNorm, _bf, stream32)
+from .blocks import (STORE, AlphaBlender, CombinedTimestepTextProjEmbeddings, JointTransformerBlock,
+                     TimestepEmbedding, VTSelfAttentionBlock, _AdaNorm, _bf, drop_caches, stream32)
 from .ops import EPI_RESID
 
 bf16 = torch.bfloat16
@@ -61,35 +61,29 @@ class PatchEmbed(nn.Module):
         self.proj = nn.Conv2d(in_channels, embed_dim, kernel_size=patch_size, stride=patch_size, bias=True)
         self.register_buffer("pos_embed", sincos_pos_embed_2d(embed_dim, pos_embed_max_size,
                                                               sample_size // patch_size), persistent=True)
-        self._cache = {}
-        self._wcache = {}
 
     def cropped(self, h: int, w: int) -> torch.Tensor:
-        from .blocks import STORE
         cd = STORE.precision
-        key = (h, w, self.pos_embed.device, self.pos_embed.data_ptr(), cd)
-        if key not in self._cache:
+
+        def make():
             m = self.pos_embed_max_size
             if h > m or w > m:
                 raise ValueError(f"Height/width ({h},{w}) exceed pos_embed_max_size {m}")
             top, left = (m - h) // 2, (m - w) // 2
             t = self.pos_embed.reshape(1, m, m, -1)[:, top:top + h, left:left + w, :]
-            self._cache = {kk: v for kk, v in self._cache.items() if kk[:4] == key[:4]}          # the other precision of this crop stays
-            self._cache[key] = t.reshape(h * w, -1).to(cd).contiguous()
-        return self._cache[key]
+            return t.reshape(h * w, -1).to(cd).contiguous()
+        # one crop per precision; independent of the weights, so it survives optimizer steps
+        return STORE.memo(self, ("pos", cd), (h, w, self.pos_embed.device, self.pos_embed.data_ptr()), make, per_step=False)
 
     def packed_weight(self):
-        from .blocks import STORE
-        key = (self.proj.weight.data_ptr(), self.proj.weight._version, STORE.step, STORE.precision)
-        if key not in self._wcache:
+        def make():
             w = self.proj.weight.detach().reshape(self.proj.weight.shape[0], -1)
             k = w.shape[1]
             kp = (k + 63) // 64 * 64
             wp = torch.zeros((w.shape[0], kp), dtype=STORE.precision, device=w.device)
             wp[:, :k] = w
-            self._wcache = {kk: v for kk, v in self._wcache.items() if kk[:3] == key[:3]}      # drop stale steps, keep the other precision
-            self._wcache[key] = wp
-        return self._wcache[key]
+            return wp
+        return STORE.memo(self, ("proj", STORE.precision), (self.proj.weight.data_ptr(), self.proj.weight._version), make)
 
     def run(self, x: torch.Tensor) -> torch.Tensor:
         """x [I, C, H, W] -> bf16 [I*h*w, D] = conv(x) + cropped pos embed."""
@@ -112,7 +106,6 @@ class RayEncoder(nn.Module):
 
     def packed(self) -> torch.Tensor:
         """proj.weight with K zero-padded 72 -> 128 (GEMM K granularity)"""
-        from .blocks import STORE
         w = self.proj.weight
 
         def make():                                   # (per compute precision: STORE.derived keys on it)
@@ -134,7 +127,6 @@ class RayEncoder(nn.Module):
         return torch.cat([torch.inverse(K).reshape(-1, 9), M[:, :3, :3].reshape(-1, 9), M[:, :3, 3]], 1).contiguous()
 
     def features(self, camera_intrinsics_norm, camera2referego, height: int, width: int) -> torch.Tensor:
-        from .blocks import STORE
         return ops.ray_features(self.camera_rows(camera_intrinsics_norm, camera2referego, height, width), height, width, 128,
                                 dtype=STORE.precision)
 
@@ -225,7 +217,6 @@ class DiTCrossviewTemporalConditionModel(_Base):
             self.condition_image_adapter = ImageAdapter(**condition_image_adapter_config)
         else:
             self.condition_image_adapter = None
-        self._adapter_cache = (None, None)
         # True: the layout residuals (step-invariant: they depend on the condition images only) are computed once, kept in
         # fp32 and re-used while the condition tensor is the same object; False: recomputed by every forward, as the
         # reference's forward does (crossview_temporal_dit.py:459-462) - then each zero convolution adds straight into the
@@ -244,7 +235,7 @@ class DiTCrossviewTemporalConditionModel(_Base):
         # round 5 (393.8 -> 392.6 ms per step, profiles/r5a_*).  Costs a packed copy of those weights (1.7 GB at full size).
         self.stack_modulation = True
         self.residual_dtype = torch.float32
-        self._index_sinusoids = {}
+        self._index_shapes = 0
         self.perspective_modeling_type = perspective_modeling_type
         if perspective_modeling_type == "implicit":
             self.view_embedding = TimestepEmbedding(projection_class_embeddings_input_dim, inner_dim)
@@ -288,28 +279,16 @@ class DiTCrossviewTemporalConditionModel(_Base):
     def enable_gradient_checkpointing(self):
         self.gradient_checkpointing = True
 
-    def _invalidate_packed(self):
-        for m in self.modules():
-            if hasattr(m, "_pk"):
-                m._pk = None
-            if hasattr(m, "_cache"):
-                m._cache = {}
-            if hasattr(m, "_wcache"):
-                m._wcache = {}
-            if hasattr(m, "_alpha_cache"):
-                m._alpha_cache = None            # AlphaBlender.get_alpha (also keyed on STORE.step, bumped below)
-        self._adapter_cache = (None, None)
-        from .blocks import STORE
-        STORE.bump()
-
     def _apply(self, fn, *a, **kw):
         out = super()._apply(fn, *a, **kw)
-        self._invalidate_packed()
+        drop_caches(self)
+        STORE.bump()
         return out
 
     def load_state_dict(self, state_dict, *a, **kw):
         out = super().load_state_dict(state_dict, *a, **kw)
-        self._invalidate_packed()
+        drop_caches(self)
+        STORE.bump()
         return out
 
     # ---- forward (crossview_temporal_dit.py:372-630)
@@ -342,7 +321,6 @@ class DiTCrossviewTemporalConditionModel(_Base):
             if kw.get("return_dict"):                       # crossview_temporal_dit.py:620-630: only the dict form is squeezed
                 return {"noise_pred": out.squeeze(2) if squeeze else out}
             return [out], None, None
-        from .blocks import STORE
         try:
             with ops.gemm_4wave_scope(self.gemm_4wave):      # this thread's launches may run on the 4-wave GEMM kernels
                 return self._forward_infer(sample, timestep, *args, **kwargs)
@@ -353,7 +331,6 @@ class DiTCrossviewTemporalConditionModel(_Base):
         """[norm1, norm1_context] modulation rows of every joint block + norm_out's, as column slices of ONE GEMM over the
         stacked `linear` weights (the packed copy lives with the other packed weights: rebuilt after an optimizer step /
         state-dict load)"""
-        from .blocks import STORE
         lins = [lin for blk in self.transformer_blocks for lin in (blk.norm1.linear, blk.norm1_context.linear)] + [self.norm_out.linear]
 
         def make():
@@ -370,23 +347,22 @@ class DiTCrossviewTemporalConditionModel(_Base):
     def _index_sinusoid(self, kind: str, B: int, T: int, V: int, D: int, device, dtype) -> torch.Tensor:
         """sinusoid features [B*T*V, D] of the frame ("t") or view ("v") index of every image (crossview_temporal_dit.py:
         528-531, 553-556): input-independent, kept on the model"""
-        key = (kind, B, T, V, D, str(device), dtype)
-        hit = self._index_sinusoids.get(key)
-        if hit is None:
+        def make():
             if kind == "t":
                 idx = torch.arange(T, device=device).view(1, T, 1).expand(B, T, V)
             else:
                 idx = torch.arange(V, device=device).view(1, 1, V).expand(B, T, V)
-            hit = ops.timestep_sinusoid(idx, D, dtype=dtype)
-            # Kept for the life of the model, never evicted: a HIP graph captured by CTSDDenoiser.enable_graph holds the POINTERS of
-            # these tensors, and freeing one a captured graph still replays would let it read recycled memory.  They are a few KiB per
-            # (batch, frames, views) shape; a model that has seen more than 64 shapes says so once instead of growing silently.
-            if len(self._index_sinusoids) == 64:
+            # One tag per shape, so no other shape evicts it: a HIP graph captured by CTSDDenoiser.enable_graph holds the POINTERS of
+            # these tensors, and freeing one a captured graph still replays would let it read recycled memory (they go with the packed
+            # weights such a graph reads, when the model's caches are dropped).  They are a few KiB per (batch, frames, views) shape;
+            # a model that has seen more than 64 shapes says so once instead of growing silently.
+            self._index_shapes += 1
+            if self._index_shapes == 65:
                 import warnings
                 warnings.warn("DiTCrossviewTemporalConditionModel: more than 64 distinct (batch, frames, views) shapes seen; the "
-                              "index-embedding cache keeps growing (entries are never freed: captured graphs may reference them)")
-            self._index_sinusoids[key] = hit
-        return hit
+                              "index-embedding cache keeps growing (entries are not evicted: captured graphs may reference them)")
+            return ops.timestep_sinusoid(idx, D, dtype=dtype)
+        return STORE.memo(self, ("sinusoid", kind, B, T, V, D, str(device), dtype), None, make, per_step=False)
 
     @staticmethod
     def _mixer_alphas(mixers, image_only_indicator, batch: int):
@@ -406,15 +382,13 @@ class DiTCrossviewTemporalConditionModel(_Base):
     # ---- cached layout residuals (the adapter is per image: a cache of [2B, T, V] images can be advanced frame by frame)
     @staticmethod
     def _adapter_cache_key(condition_image_tensor: torch.Tensor):
-        # the key holds the optimizer step (residuals of old adapter weights must not survive a training step) and
-        # the cache keeps the tensor alive (a freed tensor's address can be handed to the next same-shape batch)
-        from .blocks import STORE
-        return (condition_image_tensor.data_ptr(), condition_image_tensor._version, tuple(condition_image_tensor.shape), STORE.step)
+        # the entry (key, residuals, tensor) is per optimizer step (residuals of old adapter weights must not survive a training
+        # step) and keeps the tensor alive (a freed tensor's address can be handed to the next same-shape batch)
+        return (condition_image_tensor.data_ptr(), condition_image_tensor._version, tuple(condition_image_tensor.shape))
 
     def _cached_adapter_features(self, images: torch.Tensor, cd) -> list:
         """the residuals the cache holds for `images` [..., C, H, W]: per level fp32 [I * N, D], I = the leading dimensions.  `cd`: the
         store precision to return to (the forward's compute dtype)"""
-        from .blocks import STORE
         # Computed once per condition tensor, so it can afford the fp32 accuracy path (dwm_gemm_f32, 3 x the MFMA work of
         # the bf16 adapter, ~1 % of a 40-step loop): the adapter's error is the SAME at every denoise step and differs
         # between the conditional and the unconditional half (different layout images), so classifier-free guidance
@@ -430,8 +404,8 @@ class DiTCrossviewTemporalConditionModel(_Base):
 
     def adapter_cache_of(self, condition_image_tensor: torch.Tensor):
         """the cached residuals (per level fp32 [2B * T * V * N, D]) if the cache holds them for this very tensor as it is now, else None"""
-        c = self._adapter_cache
-        if c[0] is None or c[2] is not condition_image_tensor or c[0] != self._adapter_cache_key(condition_image_tensor):
+        c = STORE.peek(self, "adapter")
+        if c is None or c[2] is not condition_image_tensor or c[0] != self._adapter_cache_key(condition_image_tensor):
             return None
         return c[1]
 
@@ -441,7 +415,9 @@ class DiTCrossviewTemporalConditionModel(_Base):
         condition tensor takes it over and drops its reference to the residuals it held.  Whoever keeps ADDRESSES of cached
         residuals across forwards - a stream session: its captured graph and its slide tables - therefore holds the list itself
         and puts it back before its next forward."""
-        self._adapter_cache = (self._adapter_cache_key(condition_image_tensor), feats, condition_image_tensor)
+        key = self._adapter_cache_key(condition_image_tensor)
+        STORE.drop(self, "adapter")
+        STORE.memo(self, "adapter", key, lambda: (key, feats, condition_image_tensor))
 
     @torch.no_grad()
     def advance_adapter_cache(self, frame_images: torch.Tensor, out=None) -> list:
@@ -464,14 +440,14 @@ class DiTCrossviewTemporalConditionModel(_Base):
         current state as the key: for a static condition buffer that was rewritten in place while a captured graph or a FifoSlide
         plan holds the addresses of the cached residuals.  False (nothing done) if the cache holds nothing for this tensor or the
         weights have changed since."""
-        c = self._adapter_cache
-        if c[0] is None or c[2] is not condition_image_tensor or c[0][2:] != self._adapter_cache_key(condition_image_tensor)[2:]:
+        c = STORE.peek(self, "adapter")
+        if c is None or c[2] is not condition_image_tensor or c[0][2] != tuple(condition_image_tensor.shape):
             return False
         with ops.gemm_4wave_scope(self.gemm_4wave):
             feats = self._cached_adapter_features(condition_image_tensor, bf16)
         for o, f in zip(c[1], feats):
             o.copy_(f)
-        self._adapter_cache = (self._adapter_cache_key(condition_image_tensor), c[1], condition_image_tensor)
+        self.install_adapter_cache(condition_image_tensor, c[1])
         return True
 
     @torch.no_grad()
@@ -526,7 +502,6 @@ class DiTCrossviewTemporalConditionModel(_Base):
         # compute dtype: bf16 (storage bf16, fp32 accumulation / statistics), or - `model.compute_dtype = torch.float32` -
         # the fp32 accuracy path (north_star's 1e-3 tolerance; the reference runs this graph in fp32 when no autocast /
         # fp16 cast is configured, ctsd.py:1189-1193)
-        from .blocks import STORE
         cd = self.compute_dtype
         STORE.set_precision(cd)           # reset to bf16 by `forward` on the way out
 
@@ -586,12 +561,9 @@ class DiTCrossviewTemporalConditionModel(_Base):
                 (not self.cache_adapter_residuals or cd == torch.float32):      # (the fp32 accuracy path always recomputes)
             residual_adders = self.condition_image_adapter.residual_adders(condition_image_tensor)
         elif self.condition_image_adapter is not None and condition_image_tensor is not None:
-            # the key holds the optimizer step (residuals of old adapter weights must not survive a training step) and
-            # the cache keeps the tensor alive (a freed tensor's address can be handed to the next same-shape batch)
             key = self._adapter_cache_key(condition_image_tensor)
-            if self._adapter_cache[0] != key:
-                self._adapter_cache = (key, self._cached_adapter_features(condition_image_tensor, cd), condition_image_tensor)
-            condition_residuals = list(self._adapter_cache[1])
+            condition_residuals = list(STORE.memo(self, "adapter", key, lambda: (
+                key, self._cached_adapter_features(condition_image_tensor, cd), condition_image_tensor))[1])
             for f in condition_residuals:
                 if f.shape != h.shape:
                     raise RuntimeError(f"condition residual {tuple(f.shape)} does not match hidden states {tuple(h.shape)}")

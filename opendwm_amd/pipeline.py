@@ -813,27 +813,17 @@ class CTSDTrainer:
 
     def _graph_shadows(self) -> list:
         """the bf16 compute copies AdamW writes in place, as blocks.STORE holds them now (None: none, or one that is re-cast)"""
-        from .blocks import STORE
-        out = []
-        for p in self.model.parameters():
-            hit = STORE._shadow.get(id(p)) if (p.dtype == torch.float32 and p.numel() % 4 == 0 and p.is_contiguous()) else None
-            out.append(None if hit is None else hit[1])
-        return out
+        from .blocks import STORE, refreshable
+        return [STORE.shadow_of(p) if refreshable(p) else None for p in self.model.parameters()]
 
     def _graph_drop_model_caches(self) -> None:
         """every tensor the model keeps between forwards except the parameters' in-place compute copies: the capture re-creates what
         it needs inside its pool"""
-        from .blocks import STORE
-        for m in self.model.modules():
-            for name, empty in (("_pk", None), ("_cache", {}), ("_wcache", {}), ("_alpha_cache", None), ("_text_ctx", None),
-                                ("_adapter_cache", (None, None)), ("_emb_cache", (None, None, None))):
-                if hasattr(m, name):
-                    setattr(m, name, type(empty)(empty) if isinstance(empty, dict) else empty)
-            if hasattr(m, "_scratch"):
-                m._scratch = type(m._scratch)()
+        from .blocks import STORE, drop_caches, refreshable
+        drop_caches(self.model)
         for p in self.model.parameters():           # compute copies AdamW does not write: re-cast inside the capture
-            if not (p.dtype == torch.float32 and p.is_cuda and p.numel() % 4 == 0 and p.is_contiguous()):
-                STORE._shadow.pop(id(p), None)
+            if not refreshable(p):
+                STORE.forget(p)
         STORE.bump(keep_shadows=True)
 
     def _graph_capture(self, staged: dict, key: tuple, scaler) -> None:

@@ -23,7 +23,7 @@ import torch
 
 from . import ops, quant8
 from . import train_ops as T
-from .blocks import (STORE, AlphaBlender, JointTransformerBlock, TimestepEmbedding, VTSelfAttentionBlock, _bf)
+from .blocks import (STORE, AlphaBlender, JointTransformerBlock, TimestepEmbedding, VTSelfAttentionBlock, _bf, refreshable)
 from .ops import ACT_GELU_TANH, ACT_SILU
 
 bf16 = torch.bfloat16
@@ -1163,9 +1163,9 @@ class AdamW(torch.optim.Optimizer):
                     st = self._init_state(p)
                 st["step"] += 1
                 self._last_stepped.append(p)
-                shadow = STORE.bf(p) if (p.is_cuda and p.numel() % 4 == 0 and p.is_contiguous()) else None
+                shadow = STORE.bf(p) if refreshable(p) else None
                 if shadow is None:
-                    STORE._shadow.pop(id(p), None)      # re-cast on next use
+                    STORE.forget(p)                     # re-cast on next use
                 if st["exp_avg"].dtype == torch.uint8:
                     batches, row = batches8, (p.data, g, st["exp_avg"], st["exp_avg_absmax"], st["exp_avg_sq"],
                                               st["exp_avg_sq_absmax"], shadow)

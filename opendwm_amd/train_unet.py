@@ -573,7 +573,7 @@ def forward_train(model: UM.UNetCrossviewTemporalConditionModel, sample, timeste
     B, Tn, V, _, H, W = sample.shape
     dev = sample.device
     I = B * Tn * V
-    g0 = UM._Geom(B, Tn, V, H, W, model._scratch)
+    g0 = UM._Geom(B, Tn, V, H, W, model.scratch())
     if disable_crossview is None:
         disable_crossview = torch.zeros(B, dtype=torch.bool, device=dev)
     if disable_temporal is None:

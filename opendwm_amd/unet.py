@@ -25,7 +25,7 @@ from torch import nn
 
 from . import ops
 from . import train_ops as T
-from .blocks import AlphaBlender, Attention, FeedForward, TimestepEmbedding, VTSelfAttentionBlock, _bf, geglu_pack, STORE
+from .blocks import AlphaBlender, Attention, FeedForward, TimestepEmbedding, VTSelfAttentionBlock, _bf, drop_caches, geglu_pack, STORE
 from .ops import EPI_GEGLU, EPI_RESID, PaddedGrid, TimeGrid
 
 bf16 = torch.bfloat16
@@ -201,8 +201,6 @@ class _TextContext:
 
     def __init__(self, encoder_hidden_states: torch.Tensor):
         self.source = encoder_hidden_states                  # held: its storage cannot be recycled under the cache key
-        self.key = (encoder_hidden_states.data_ptr(), encoder_hidden_states._version, tuple(encoder_hidden_states.shape),
-                    encoder_hidden_states.dtype, STORE.step, STORE.precision)
         ehs = encoder_hidden_states.flatten(0, -3)
         ehs = ehs if ehs.dtype == STORE.precision else ehs.to(STORE.precision)
         self.rows = ehs.reshape(ehs.shape[0] * ehs.shape[1], -1).contiguous()
@@ -212,12 +210,8 @@ class _TextContext:
     def from_rows(cls, rows: torch.Tensor) -> "_TextContext":
         """a context over text rows that are already flattened to [images * L, cross_attention_dim] bf16 (training path)"""
         self = cls.__new__(cls)
-        self.source, self.key, self.rows, self._kv = None, None, rows, {}
+        self.source, self.rows, self._kv = None, rows, {}
         return self
-
-    def matches(self, encoder_hidden_states: torch.Tensor) -> bool:
-        t = encoder_hidden_states
-        return t is self.source and self.key == (t.data_ptr(), t._version, tuple(t.shape), t.dtype, STORE.step, STORE.precision)
 
     def kv(self, attn: "_CrossAttention") -> torch.Tensor:
         out = self._kv.get(id(attn))
@@ -298,7 +292,6 @@ class TransformerModel(nn.Module):
         else:
             self.time_pos_embed = None
         self.proj_out = nn.Linear(inner, in_channels)
-        self._emb_cache = (None, None, None)
 
     def run(self, x: torch.Tensor, ctx: "_TextContext", g: _Geom, disable_crossview, disable_temporal, mask) -> torch.Tensor:
         B, Tn, V, C = g.B, g.T, g.V, self.in_channels
@@ -306,8 +299,7 @@ class TransformerModel(nn.Module):
         hn = ops.groupnorm_silu(x, g.I, g.N, _bf(self.norm.weight), _bf(self.norm.bias), 32, 1e-6, silu=False)
         h = ops.gemm(hn, _bf(self.proj_in.weight), _bf(self.proj_in.bias))
         # view / frame index embeddings depend on (B, T, V) and the weights only: kept across denoise steps
-        key = (STORE.step, B, Tn, V, str(dev), STORE.precision)
-        if self._emb_cache[0] != key:
+        def index_embeddings():
             view_emb = seq_emb = None
             if self.view_pos_embed is not None:
                 idx = torch.arange(V, device=dev).view(1, 1, V).expand(B, Tn, V)
@@ -315,8 +307,8 @@ class TransformerModel(nn.Module):
             if self.time_pos_embed is not None:
                 idx = torch.arange(Tn, device=dev).view(1, Tn, 1).expand(B, Tn, V)
                 seq_emb = self.time_pos_embed.run(ops.timestep_sinusoid(idx, C, dtype=STORE.precision))
-            self._emb_cache = (key, view_emb, seq_emb)
-        _, view_emb, seq_emb = self._emb_cache
+            return view_emb, seq_emb
+        view_emb, seq_emb = STORE.memo(self, "emb", (B, Tn, V, str(dev), STORE.precision), index_embeddings)
         if self.view_pos_embed is not None:
             alpha_v = self.view_mixer.get_alpha(disable_crossview, B)
         if self.time_pos_embed is not None:
@@ -447,12 +439,9 @@ class UNetCrossviewTemporalConditionModel(_Base):
         if condition_image_adapter_config is not None:                  # crossview_temporal_unet.py: layout ImageAdapter
             from .adapters import ImageAdapter
             self.condition_image_adapter = ImageAdapter(**condition_image_adapter_config)
-        self._adapter_cache = (None, None)
         self.depth_net = None
         self.gradient_checkpointing = False
         self.depth_frustum_range = depth_frustum_range
-        self._scratch = _Scratch()
-        self._text_ctx = None
         self._tproj_layers = None
 
     def enable_gradient_checkpointing(self):
@@ -481,16 +470,19 @@ class UNetCrossviewTemporalConditionModel(_Base):
 
     def _apply(self, fn, *a, **kw):
         out = super()._apply(fn, *a, **kw)
+        drop_caches(self)
         STORE.bump()
-        self._scratch = _Scratch()
-        self._text_ctx = None
-        self._adapter_cache = (None, None)
         return out
 
     def load_state_dict(self, state_dict, *a, **kw):
         out = super().load_state_dict(state_dict, *a, **kw)
+        drop_caches(self)
         STORE.bump()
         return out
+
+    def scratch(self) -> _Scratch:
+        """the zero-bordered padded buffers of this model: independent of the weights, so they survive optimizer steps"""
+        return STORE.memo(self, "scratch", None, _Scratch, per_step=False)
 
     def forward(self, sample: torch.Tensor, timesteps, frustum_bev_residuals=None, encoder_hidden_states=None,
                 condition_image_tensor=None, disable_crossview=None, disable_temporal=None, crossview_attention_mask=None,
@@ -563,7 +555,8 @@ class UNetCrossviewTemporalConditionModel(_Base):
         B, Tn, V, Cin, H, W = sample.shape
         dev = sample.device
         I = B * Tn * V
-        g0 = _Geom(B, Tn, V, H, W, self._scratch)
+        scratch = self.scratch()
+        g0 = _Geom(B, Tn, V, H, W, scratch)
         if disable_crossview is None:
             disable_crossview = torch.zeros(B, dtype=torch.bool, device=dev)
         if disable_temporal is None:
@@ -576,9 +569,9 @@ class UNetCrossviewTemporalConditionModel(_Base):
             aug = ops.timestep_sinusoid(added_time_ids.flatten(), self.addition_time_embed_dim, dtype=cd).view(I, -1)
             emb = self.add_embedding.run(aug, res=emb)
         silu_emb = _TimeProj(self._time_proj_layers(), ops.silu(emb))
-        if self._text_ctx is None or not self._text_ctx.matches(encoder_hidden_states):
-            self._text_ctx = _TextContext(encoder_hidden_states)
-        ctx = self._text_ctx
+        ehs = encoder_hidden_states             # (the context holds the tensor, so its id() stays its own under this key)
+        ctx = STORE.memo(self, "text", (id(ehs), ehs.data_ptr(), ehs._version, tuple(ehs.shape), ehs.dtype, cd),
+                         lambda: _TextContext(ehs))
 
         # 2. conv_in: NCHW -> token-major rows with the channels zero-padded to 64, 3x3 implicit GEMM
         xin = sample.flatten(0, 2).contiguous()
@@ -588,17 +581,16 @@ class UNetCrossviewTemporalConditionModel(_Base):
             xin = xin.to(bf16)
         tok = ops.unshuffle_tokens(xin, 1, 64, dtype=cd)
         grid = PaddedGrid(I, H, W)
-        pin = ops.pad_tokens(tok, grid, out=self._scratch.get("in", grid.rows, 64, dev))
+        pin = ops.pad_tokens(tok, grid, out=scratch.get("in", grid.rows, 64, dev))
         wci = STORE.derived(self.conv_in.weight, "c3", lambda: _conv3_w(self.conv_in.weight, c_pad=64))
         x = ops.gemm(pin, wci, _bf(self.conv_in.bias), a_grid=grid, conv3x3=True)
         # layout residuals (:717-729, 748-750): one after conv_in, one after every down block - added in place, so the
         # block's last skip connection carries the sum as in the reference.  Step-invariant: cached on the tensor identity.
         residuals = []
         if self.condition_image_adapter is not None and condition_image_tensor is not None:
-            key = (condition_image_tensor.data_ptr(), condition_image_tensor._version, tuple(condition_image_tensor.shape), STORE.step)
-            if self._adapter_cache[0] != key:
-                self._adapter_cache = (key, self.condition_image_adapter.run(condition_image_tensor, precise=True), condition_image_tensor)
-            residuals = list(self._adapter_cache[1])
+            key = (condition_image_tensor.data_ptr(), condition_image_tensor._version, tuple(condition_image_tensor.shape))
+            residuals = list(STORE.memo(self, "adapter", key, lambda: (
+                self.condition_image_adapter.run(condition_image_tensor, precise=True), condition_image_tensor))[0])
 
         def add_residual(t):
             if residuals:
@@ -621,7 +613,7 @@ class UNetCrossviewTemporalConditionModel(_Base):
             if blk.downsamplers is not None:
                 conv = blk.downsamplers[0].conv
                 gr = PaddedGrid(I, h_, w_)
-                pad = ops.pad_tokens(x, gr, out=self._scratch.get("ds", gr.rows, x.shape[1], dev))
+                pad = ops.pad_tokens(x, gr, out=scratch.get("ds", gr.rows, x.shape[1], dev))
                 wd = STORE.derived(conv.weight, "c3", lambda: _conv3_w(conv.weight))
                 x = ops.gemm(pad, wd, _bf(conv.bias), a_grid=gr, conv3x3=True, stride2="sym")
                 h_, w_ = h_ // 2, w_ // 2
@@ -645,14 +637,14 @@ class UNetCrossviewTemporalConditionModel(_Base):
             if blk.upsamplers is not None:
                 conv = blk.upsamplers[0].conv
                 gr = PaddedGrid(I, 2 * h_, 2 * w_)
-                up = ops.upsample2_padded(x, I, h_, w_, out=self._scratch.get("us", gr.rows, x.shape[1], dev))
+                up = ops.upsample2_padded(x, I, h_, w_, out=scratch.get("us", gr.rows, x.shape[1], dev))
                 wu = STORE.derived(conv.weight, "c3", lambda: _conv3_w(conv.weight))
                 x = ops.gemm(up, wu, _bf(conv.bias), a_grid=gr, conv3x3=True)
                 h_, w_ = 2 * h_, 2 * w_
         # 6. head: GroupNorm -> SiLU -> conv_out (output channels padded to 8 for the GEMM, dropped by the un-tokenizer)
         gr = PaddedGrid(I, H, W)
         pn = ops.groupnorm_silu(x, I, H * W, _bf(self.conv_norm_out.weight), _bf(self.conv_norm_out.bias), 32, 1e-5,
-                                out=self._scratch.get("s1", gr.rows, x.shape[1], dev), out_grid=gr)
+                                out=scratch.get("s1", gr.rows, x.shape[1], dev), out_grid=gr)
         co = self.out_channels_
         cop = (co + 7) // 8 * 8
         wco = STORE.derived(self.conv_out.weight, "c3", lambda: _conv3_w(self.conv_out.weight, n_pad=cop))

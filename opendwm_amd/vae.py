@@ -12,16 +12,22 @@ attention is one fused kernel (csrc/vae_attention.hip), so any size encodes and 
 from __future__ import annotations
 
 import types
-from typing import Dict, Optional, Tuple
+from typing import Optional
 
 import torch
 from torch import nn
 
 from . import ops
-from .blocks import STORE, _bf
+from .blocks import STORE, _bf, drop_caches
 from .ops import EPI_RESID, PaddedGrid
 
 bf16 = torch.bfloat16
+
+
+def _weights_key(*tensors) -> tuple:
+    """memo key of packs of a frozen model: the weights as they are now, not the optimizer step (a state-dict load or `.to()`
+    rebuilds them, a training step of another model does not)"""
+    return tuple((t.data_ptr(), t._version) for t in tensors)
 
 
 def _conv3_w(conv: nn.Conv2d, k_pad: Optional[int] = None) -> torch.Tensor:
@@ -45,15 +51,17 @@ class ResnetBlock2D(nn.Module):
         self.norm2 = nn.GroupNorm(groups, out_channels, eps=eps)
         self.conv2 = nn.Conv2d(out_channels, out_channels, 3, padding=1)
         self.conv_shortcut = nn.Conv2d(in_channels, out_channels, 1) if in_channels != out_channels else None
-        self._pk = {}
 
     def packed(self):
-        pk = self._pk.get(STORE.precision)                    # one set per compute precision (bf16 / the fp32 accuracy path)
-        if pk is None:
-            pk = self._pk[STORE.precision] = {"w1": _conv3_w(self.conv1), "w2": _conv3_w(self.conv2)}
+        convs = [c for c in (self.conv1, self.conv2, self.conv_shortcut) if c is not None]
+
+        def make():
+            pk = {"w1": _conv3_w(self.conv1), "w2": _conv3_w(self.conv2)}
             if self.conv_shortcut is not None:
                 pk["ws"] = _bf(self.conv_shortcut.weight).reshape(self.conv_shortcut.weight.shape[0], -1).contiguous()
-        return pk
+            return pk
+        # one set per compute precision (bf16 / the fp32 accuracy path)
+        return STORE.memo(self, ("packed", STORE.precision), _weights_key(*(c.weight for c in convs)), make, per_step=False)
 
     def run(self, x: torch.Tensor, grid: PaddedGrid, scratch) -> torch.Tensor:
         pk = self.packed()
@@ -113,16 +121,13 @@ class _VaeAttention(nn.Module):
         self.to_k = nn.Linear(channels, channels)
         self.to_v = nn.Linear(channels, channels)
         self.to_out = nn.ModuleList([nn.Linear(channels, channels), nn.Identity()])
-        self._pk = {}
 
     def packed(self):
         """q | k | v weights [3C, C] and biases [3C] of the fused route, one set per compute precision"""
-        pk = self._pk.get(STORE.precision)
-        if pk is None:
-            qkv = (self.to_q, self.to_k, self.to_v)
-            pk = self._pk[STORE.precision] = {"w": torch.cat([_bf(m.weight) for m in qkv], 0).contiguous(),
-                                              "b": torch.cat([_bf(m.bias) for m in qkv], 0).contiguous()}
-        return pk
+        qkv = (self.to_q, self.to_k, self.to_v)
+        return STORE.memo(self, ("packed", STORE.precision), _weights_key(*(t for m in qkv for t in (m.weight, m.bias))),
+                          lambda: {"w": torch.cat([_bf(m.weight) for m in qkv], 0).contiguous(),
+                                   "b": torch.cat([_bf(m.bias) for m in qkv], 0).contiguous()}, per_step=False)
 
     def run(self, x: torch.Tensor, I: int, P: int, mode: str = "auto") -> torch.Tensor:
         Cc = self.channels
@@ -261,7 +266,6 @@ class AutoencoderKL(nn.Module):
                                             latent_channels=latent_channels, block_out_channels=tuple(block_out_channels),
                                             in_channels=in_channels, out_channels=out_channels,
                                             layers_per_block=layers_per_block, norm_num_groups=norm_num_groups)
-        self._scratch: Dict[Tuple[int, int], torch.Tensor] = {}
         # torch.float32 selects the fp32 accuracy path of encode / decode (north_star's 1e-3 tolerance; the reference's CPU path,
         # BASELINE.json configs[0], decodes in fp32: ctsd.py:1189-1193, 1634-1640): fp32 activations and weights, convolutions
         # by dwm_gemm_f32, fp32 GroupNorm / softmax kernels
@@ -294,16 +298,22 @@ class AutoencoderKL(nn.Module):
         model.load_state_dict(sd)
         return model.eval()
 
+    def _apply(self, fn, *a, **kw):
+        out = super()._apply(fn, *a, **kw)
+        drop_caches(self)
+        return out
+
+    def load_state_dict(self, state_dict, *a, **kw):
+        out = super().load_state_dict(state_dict, *a, **kw)
+        drop_caches(self)
+        return out
+
     def _pad_scratch(self, grid: PaddedGrid, channels: int) -> torch.Tensor:
-        """zero-bordered padded buffers, reused (every producer rewrites the whole interior)."""
-        key = (grid.I, grid.h, grid.w, channels, STORE.precision)
+        """zero-bordered padded buffers, reused (every producer rewrites the whole interior): one per level, channel count and
+        precision, so the levels of one encode / decode do not evict each other; replaced when the image count changes"""
         dev = self.decoder.conv_in.weight.device
-        buf = self._scratch.get(key)
-        if buf is None or buf.device != dev:
-            self._scratch = {k: v for k, v in self._scratch.items() if k[:3] == key[:3]}   # drop other resolutions
-            buf = torch.zeros((grid.rows, channels), dtype=STORE.precision, device=dev)
-            self._scratch[key] = buf
-        return buf
+        return STORE.memo(self, ("scratch", grid.h, grid.w, channels, STORE.precision), (grid.I, dev),
+                          lambda: torch.zeros((grid.rows, channels), dtype=STORE.precision, device=dev), per_step=False)
 
     @torch.no_grad()
     def encode(self, x: torch.Tensor, return_dict: bool = True, chunk: int = 8):

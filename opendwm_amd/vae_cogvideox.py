@@ -30,7 +30,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .blocks import STORE, _bf
+from .blocks import STORE, _bf, drop_caches
 from .ops import EPI_RESID, Grid3D, PaddedGrid
 from .vae import AutoencoderKL, DiagonalGaussianDistribution, _conv3_w
 
@@ -198,8 +198,6 @@ class AutoencoderKLCogVideoX(nn.Module):
         # causal 3x3x3 convolutions through dwm_gemm_f32 (27 taps as three groups of 9), GroupNorm / spatial norm / frame mixes /
         # resampling in their fp32 forms; the reference runs this VAE in whatever dtype the caller loaded it in
         self.compute_dtype = bf16
-        self._scratch: Dict[tuple, torch.Tensor] = {}
-        self._packed: Dict[int, torch.Tensor] = {}
 
     from_pretrained = classmethod(AutoencoderKL.from_pretrained.__func__)
 
@@ -209,30 +207,26 @@ class AutoencoderKLCogVideoX(nn.Module):
 
     def _apply(self, fn, *a, **kw):
         out = super()._apply(fn, *a, **kw)
-        self._scratch, self._packed = {}, {}
+        drop_caches(self)
         return out
 
     def load_state_dict(self, state_dict, *a, **kw):
         out = super().load_state_dict(state_dict, *a, **kw)
-        self._packed = {}
+        drop_caches(self)
         return out
 
     # ------------------------------------------------------------------ helpers
-    def packed(self, module: nn.Module, make) -> torch.Tensor:
-        key = (id(module), STORE.precision)                  # one set per compute precision
-        t = self._packed.get(key)
-        if t is None:
-            t = self._packed[key] = make()
-        return t
+    @staticmethod
+    def packed(module: nn.Module, make) -> torch.Tensor:
+        """the packed operand `make()` builds from `module` (a frozen model: kept until the caches are dropped), per precision"""
+        return STORE.memo(module, ("packed", STORE.precision), None, make, per_step=False)
 
     def scratch(self, grid, channels: int) -> torch.Tensor:
         """zero-bordered padded buffers, reused: every producer rewrites the whole interior, the border stays zero"""
         key = (type(grid).__name__,) + tuple(getattr(grid, f) for f in grid.__dataclass_fields__) + (channels, STORE.precision)
         dev = self.decoder.conv_in.conv.weight.device
-        buf = self._scratch.get(key)
-        if buf is None or buf.device != dev:
-            buf = self._scratch[key] = torch.zeros((grid.rows, channels), dtype=STORE.precision, device=dev)
-        return buf
+        return STORE.memo(self, ("scratch",) + key, dev, lambda: torch.zeros((grid.rows, channels), dtype=STORE.precision, device=dev),
+                          per_step=False)
 
     @staticmethod
     def _conv27_w(conv: nn.Conv3d, k_pad: Optional[int] = None, n_pad: Optional[int] = None) -> torch.Tensor:

@@ -27,6 +27,7 @@ sys.path.insert(0, ROOT)
 
 import bench                                   # noqa: E402
 from opendwm_amd import ops                    # noqa: E402
+from opendwm_amd.blocks import STORE           # noqa: E402
 from opendwm_amd.pipeline import CTSDDenoiser  # noqa: E402
 from oracle import ctsd_oracle as O            # noqa: E402  (checker only)
 
@@ -135,10 +136,10 @@ def main():
                 model.cache_adapter_residuals = True
                 run00 = model.condition_image_adapter.run
                 model.condition_image_adapter.run = lambda x, precise=False: run00(x, precise=False)
-                model._adapter_cache = (None, None)
+                STORE.drop(model, "adapter")
                 results.append(analyse(name + "/bf16_adapter_round2", *run_product(model, lat, cond, traj), traj))
                 model.condition_image_adapter.run = run00
-                model._adapter_cache = (None, None)
+                STORE.drop(model, "adapter")
                 # the adapter's residuals from the fp32 oracle instead of the bf16 HIP adapter
                 with torch.no_grad():
                     feats = O.image_adapter(sd, cfg, condf["condition_image_tensor"])
@@ -146,7 +147,7 @@ def main():
                 run0 = model.condition_image_adapter.run
                 # (a) oracle residuals rounded to bf16, added by the bf16 add kernel
                 model.condition_image_adapter.run = lambda x, precise=False: [t.to(bf16) for t in tok]
-                model._adapter_cache = (None, None)
+                STORE.drop(model, "adapter")
                 results.append(analyse(name + "/oracle_residuals_bf16", *run_product(model, lat, cond, traj), traj))
                 # (b) oracle residuals kept in fp32 and added in fp32 (one rounding of the sum)
                 add0 = ops.add_
@@ -158,13 +159,13 @@ def main():
                     return add0(h, r)
                 import opendwm_amd.dit as dit
                 model.condition_image_adapter.run = lambda x, precise=False: list(tok)
-                model._adapter_cache = (None, None)
+                STORE.drop(model, "adapter")
                 dit.ops.add_ = add_fp32
                 try:
                     results.append(analyse(name + "/oracle_residuals_fp32_add", *run_product(model, lat, cond, traj), traj))
                     # (c) the HIP adapter's own bf16 residuals, but added in fp32 (isolates the bf16 add)
                     model.condition_image_adapter.run = lambda x, precise=False: [t.float() for t in run0(x, precise=False)]
-                    model._adapter_cache = (None, None)
+                    STORE.drop(model, "adapter")
                     results.append(analyse(name + "/hip_residuals_fp32_add", *run_product(model, lat, cond, traj), traj))
                 finally:
                     dit.ops.add_ = add0

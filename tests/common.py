@@ -50,6 +50,40 @@ def to_dev(d, device, float_dtype=None):
     return out
 
 
+def held_tensors(model) -> list:
+    """every tensor a module of `model` holds in a plain attribute: reachable from a module's __dict__ other than through
+    `_parameters`, `_buffers` and `_modules`, through dicts, lists, tuples, sets and objects with a __dict__.  Knows no attribute
+    names: a cache under any name is found.  Parameters and buffers themselves (a list of layers kept for convenience leads to
+    them) are not `held`."""
+    own = {id(t) for t in list(model.parameters()) + list(model.buffers())}
+    seen, found = set(), []
+
+    def walk(o):
+        if id(o) in seen or o is None or isinstance(o, (str, bytes, int, float, bool, torch.dtype, torch.device, type)):
+            return
+        seen.add(id(o))
+        if torch.is_tensor(o):
+            if id(o) not in own:
+                found.append(o)
+        elif isinstance(o, dict):
+            for k, v in o.items():
+                walk(k)
+                walk(v)
+        elif isinstance(o, (list, tuple, set, frozenset)):
+            for v in o:
+                walk(v)
+        elif isinstance(o, torch.nn.Module):
+            for k, v in vars(o).items():
+                if k not in ("_parameters", "_buffers", "_modules"):
+                    walk(v)
+        elif hasattr(o, "__dict__") and not callable(o):
+            walk(vars(o))
+
+    for m in model.modules():
+        walk(m)
+    return found
+
+
 import contextlib
 
 

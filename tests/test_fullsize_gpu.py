@@ -149,16 +149,17 @@ def test_full_size_layout_adapter_and_pointwise_temporal(full_layout):
       * with the mixing branches disabled the forward is per image: permuting the frames - latents, text, time ids AND
         condition images - permutes the prediction exactly (checks the adapter's padded-grid convolutions and the
         residual addressing at full size)."""
+    from opendwm_amd.blocks import STORE
     model, cond, x, ts, dev = full_layout
     B2, T, V = x.shape[:3]
-    model._adapter_cache = (None, None)
+    STORE.drop(model, "adapter")
     model.cache_adapter_residuals = True
     model.adapter_cache_dtype = torch.float32                      # (default) cached residuals through the fp32 path
     p32 = fwd(model, x, ts, cond)
-    model._adapter_cache = (None, None)
+    STORE.drop(model, "adapter")
     model.adapter_cache_dtype = torch.bfloat16                     # the same arithmetic as the per-step recompute
     a = fwd(model, x, ts, cond)
-    assert model._adapter_cache[0] is not None
+    assert model.adapter_cache_of(cond["condition_image_tensor"]) is not None
     b = fwd(model, x, ts, cond)                                    # cached fp32 residuals, added by dwm_add_f32_f32_inplace
     model.cache_adapter_residuals = False
     c = fwd(model, x, ts, cond)                                    # recomputed, zero convolutions adding from their GEMM epilogues

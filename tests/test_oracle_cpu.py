@@ -236,15 +236,15 @@ def test_packed_prescaled_rms_weights_are_each_norm_s_own():
         n.weight.data = 1 + 0.5 * torch.randn(64, generator=g)
     c = 64 ** -0.5 * 1.4426950408889634
     from opendwm_amd.blocks import STORE
-    before = set(STORE._shadow)
+    before = STORE.shadow_ids()
     for _ in range(3):                                                # (fresh temporaries each time)
-        a._pk = None
+        STORE.drop(a)
         pk = a.packed()
         for key, nq, nk in (("rms", a.norm_q, a.norm_k), ("rms_add", a.norm_added_q, a.norm_added_k)):
             assert torch.equal(pk[key], torch.cat([nq.weight.to(bf16).repeat(2), nk.weight.to(bf16).repeat(2)]))
             assert torch.equal(pk[key + "_ps"], torch.cat([(nq.weight.float() * c).to(bf16).repeat(2), nk.weight.to(bf16).repeat(2)]))
         # ... and no temporary may sit in the identity-keyed cache at all (the stale hit itself needs the allocator's cooperation)
-        assert {k for k in STORE._shadow if k not in before} <= {id(p) for p in a.parameters()}
+        assert STORE.shadow_ids() - before <= {id(p) for p in a.parameters()}
         STORE.bump()
 
 

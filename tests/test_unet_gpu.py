@@ -239,6 +239,7 @@ def test_unet_with_layout_adapter_vs_oracle(dev):
     """condition_image_tensor -> ImageAdapter -> residuals after conv_in and after every down block
     (crossview_temporal_unet.py:717-755): forward against the oracle, and the step-invariant adapter cache"""
     from oracle import unet_oracle as U
+    from opendwm_amd.blocks import STORE
     from opendwm_amd.unet import UNetCrossviewTemporalConditionModel
     acfg = dict(in_channels=3, channels=[128, 128, 256, 512, 512], is_downblocks=[False, True, True, True, False],
                 num_res_blocks=1, downscale_factor=8, use_zero_convs=True)
@@ -259,7 +260,7 @@ def test_unet_with_layout_adapter_vs_oracle(dev):
     assert e < TOL_MODEL and rel_err(ref, plain) > 5e-2
     kw = dict(di)
     again = m(to_dev(inp, dev)["sample"], to_dev(inp, dev)["timesteps"], **kw)[0][0]      # same tensor object: cached residuals
-    assert torch.equal(again, out) and m._adapter_cache[0] is not None          # also: GroupNorm statistics are order-fixed
+    assert torch.equal(again, out) and STORE.peek(m, "adapter") is not None       # also: GroupNorm statistics are order-fixed
 
 
 @pytest.mark.parametrize("name", ["rowwise", "pointwise"])
