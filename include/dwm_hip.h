@@ -765,7 +765,9 @@ int dwm_cast_bf16_to_f32(const void* x, int64_t ldx, float* y, int64_t ldy, int6
  * Implicit convolution as in dwm_gemm_bf16 (a_map / c_map / tap_shift, up to 27 taps): W = [ hi_t | lo_t | hi_t ] per tap t, taps in
  * groups of 9 (group g = [N, 9 * 3 * k_per_tap] contiguous, groups one after the other; <= 9 taps: one group = the plain [N, 3K]).
  * workspace (16-byte aligned): the two bf16 planes of A (4 * A rows * k_per_tap bytes, + 256) followed by the fp32 partial sums,
- * 4*M*N bytes per group of taps (more, if given, lets the call split K over ranges when the tile grid is small). */
+ * 4*M*N bytes per group of taps (more, if given, lets the call split K over ranges when the tile grid is small).
+ * split_k = 1 forbids that split whatever the workspace holds - the order in which a row's products are summed then does not
+ * depend on M (the text encoders' row-independence guarantee); every other value leaves the choice to the rule above. */
 int dwm_gemm_f32(const dwm_gemm_args* args, void* stream);
 /* fp32-I/O forms of the token-major glue kernels of the SD 2.1 UNet / the 2-D VAE / the layout ImageAdapter (same argument meaning
  * as the bf16 entry points above; gamma / beta fp32): GroupNorm(+SiLU) incl. the row-mapped form of TemporalResnetBlock
@@ -801,7 +803,8 @@ int dwm_cfg_euler_step_f32(const float* pred, float* latents, float* model_in, i
  * Text encoders (opendwm_amd/text_encoders.py): the frozen CLIP-L / CLIP-G / T5-XXL encoders `get_conditions` calls
  * (src/dwm/pipelines/ctsd.py:186-192, :205-253, :744-804; in the reference: transformers CLIPTextModel,
  * CLIPTextModelWithProjection and T5EncoderModel).  Their linear layers are dwm_gemm_bf16, CLIP's norms dwm_layernorm_x32;
- * below is what those do not cover.  bf16 path only.
+ * below is what those do not cover.  Every entry has an fp32 twin (`_f32`, further down) for the fp32 accuracy path of the
+ * encoders, whose linear layers are dwm_gemm_f32 (split_k = 1) and whose CLIP norms are dwm_layernorm_f32.
  *
  * dwm_text_attention: out[s*L + i, h*64 + d] = sum_j softmax_j(x_ij) v[s*L + j, h*64 + d],
  *   x_ij = scale * <q[s*L + i, h*64 ..], k[s*L + j, h*64 ..]> + (bias ? bias[h, i, j] : 0),  j in [0, L) and, with causal = 1,
@@ -838,6 +841,26 @@ int dwm_text_embed(const int64_t* ids, int64_t n, const void* table_bf16, int64_
  * this), j < F; bf16 in / out, computed in fp32.  kind 0: quick-GELU x sigmoid(1.702 x) (CLIP-L); 1: erf-GELU (CLIP-G, the SD 2.1
  * CLIP); 2: tanh-GELU (T5's gelu_new).  F % 8 == 0. */
 int dwm_text_act(const void* x, int64_t ldx, int64_t rows, int64_t F, int32_t kind, int32_t gated, void* y, int64_t ldy, void* stream);
+
+/* The fp32 accuracy path of the text encoders: the four entries above with fp32 operands.  Arguments, semantics and refusals are
+ * those of the bf16 twin unless said otherwise; strides count fp32 elements (multiples of 4 instead of 8 where the twin's operand
+ * was bf16), pointers are 16-byte aligned.
+ *
+ * dwm_text_attention_f32: the same dwm_text_attn_args with fp32 q / k / v / out.  Both contractions are fp32 fused multiply-adds
+ *   on the unrounded operands (no bf16 rounding of Q, K, P, V or O), the exponential is the correctly-rounded-to-an-ulp library
+ *   form, the row maximum is exact, keys >= L and causally excluded keys are removed by selection, nothing outside rows
+ *   [0, n_seq*L) is addressed, the summation order is fixed (deterministic).  One workgroup per (sequence, head).
+ * dwm_rmsnorm_rows_f32: fp32 x -> fp32 y with an fp32 weight.
+ * dwm_text_embed_f32: fp32 tables -> the fp32 stream (ids clamped into [0, vocab) before an address is formed).
+ * dwm_text_act_f32: fp32 in / out; the same tail-accurate formulations (0.5 x erfc(-x / sqrt 2) for kind 1, the exponent-domain
+ *   product in the deep negative tail of kind 2) on the library's exp / erfc / log, not on the hardware approximations. */
+int dwm_text_attention_f32(const dwm_text_attn_args* args, void* stream);
+int dwm_rmsnorm_rows_f32(const float* x, int64_t ldx, int64_t rows, int64_t D, const float* w, float eps, float* y, int64_t ldy,
+                         void* stream);
+int dwm_text_embed_f32(const int64_t* ids, int64_t n, const float* table, int64_t vocab, int64_t D, const float* pos_table, int64_t L,
+                       float* out, int64_t ldo, void* stream);
+int dwm_text_act_f32(const float* x, int64_t ldx, int64_t rows, int64_t F, int32_t kind, int32_t gated, float* y, int64_t ldy,
+                     void* stream);
 
 /* ------------------------------------------------------------------------
  * NF4 4-bit weights (opendwm_amd/nf4.py, csrc/gemm_nf4.hip): the `load_in_4bit`, `bnb_4bit_quant_type="nf4"` option of the text

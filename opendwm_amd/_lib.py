@@ -246,6 +246,10 @@ SIGNATURES = {
     "dwm_rmsnorm_rows": (_i32, [_vp, _i64, _i64, _i64, _vp, _f32, _vp, _i64, _vp]),
     "dwm_text_embed": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "dwm_text_act": (_i32, [_vp, _i64, _i64, _i64, _i32, _i32, _vp, _i64, _vp]),
+    "dwm_text_attention_f32": (_i32, [C.POINTER(TextAttnArgs), _vp]),
+    "dwm_rmsnorm_rows_f32": (_i32, [_vp, _i64, _i64, _i64, _vp, _f32, _vp, _i64, _vp]),
+    "dwm_text_embed_f32": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "dwm_text_act_f32": (_i32, [_vp, _i64, _i64, _i64, _i32, _i32, _vp, _i64, _vp]),
     # NF4 4-bit weights
     "dwm_nf4_quantize": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "dwm_nf4_dequantize": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),

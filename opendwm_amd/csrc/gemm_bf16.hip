@@ -1159,7 +1159,7 @@ extern "C" int dwm_gemm_f32(const dwm_gemm_args* a, void* stream) {
     const int last_taps = ctaps - 9 * (ngroups - 1);
     const int64_t tiles = (int64_t)pl.ntm * pl.ntn, nk = 3 * kpt * last_taps / BK, slice_bytes = a->M * a->N * 4;
     pl.ksplit = 1;
-    if (splitk_pays(tiles * ngroups, nk))
+    if (a->split_k != 1 && splitk_pays(tiles * ngroups, nk))     // split_k = 1: the caller forbids K ranges (a row's sum must not depend on M)
         pl.ksplit = clamp_ksplit((int)(256 / (tiles * ngroups)), nk, 32 / ngroups, ngroups * slice_bytes, a->workspace_bytes - plane_bytes);
     if (pl.ksplit < 1) pl.ksplit = 1;
     if (plane_bytes + (int64_t)ngroups * slice_bytes > a->workspace_bytes) return DWM_EINVAL;

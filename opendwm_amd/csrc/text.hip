@@ -5,6 +5,8 @@
 //   dwm_rmsnorm_rows     T5LayerNorm: whole-row RMS norm of the fp32 residual stream, bf16 out
 //   dwm_text_embed       token (+ position) embedding gather into the fp32 residual stream
 //   dwm_text_act         quick-GELU / erf-GELU / tanh-GELU on bf16, plain or gated (act(x[:, :F]) * x[:, F:])
+//   dwm_*_f32            the four above with fp32 operands: the fp32 accuracy path of the encoders (text_attn_f32_kernel and the
+//                        float instantiations of the other three; exact fp32 contractions, library exp / erfc / log)
 //
 // Attention (text_attn_kernel): ONE wave per (sequence, head), 4 waves = 4 (sequence, head) items per workgroup, no data shared
 // between waves.  A wave stages its head's K rows ([128][64] bf16, row pitch 144 B: conflict-free 16-byte row reads) and V
@@ -170,9 +172,11 @@ text_attn_kernel(const TaParams p) {
 }
 
 // ---- T5LayerNorm: y = x rsqrt(mean(x^2) + eps) w; one workgroup per row, the row stays in registers (D <= 8192 = 256 x 4 x 8)
+// (T: element type of w and y - bf16_t, or float on the fp32 accuracy path)
+template <typename T>
 __global__ void __launch_bounds__(256)
-rmsnorm_rows_kernel(const float* __restrict__ x, int64_t ldx, int D, const bf16_t* __restrict__ w, float eps,
-                    bf16_t* __restrict__ y, int64_t ldy) {
+rmsnorm_rows_kernel(const float* __restrict__ x, int64_t ldx, int D, const T* __restrict__ w, float eps,
+                    T* __restrict__ y, int64_t ldy) {
     __shared__ float part[4];
     const int tid = threadIdx.x;
     const int nch = D >> 3;
@@ -193,36 +197,37 @@ rmsnorm_rows_kernel(const float* __restrict__ x, int64_t ldx, int D, const bf16_
     __syncthreads();
     const float tot = (part[0] + part[1]) + (part[2] + part[3]);
     const float r = 1.f / sqrtf(tot / (float)D + eps);
-    bf16_t* const yr = y + (int64_t)blockIdx.x * ldy;
+    T* const yr = y + (int64_t)blockIdx.x * ldy;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int ch = tid + 256 * i;
         if (ch < nch) {
             float g[8], f[8];
-            load8<bf16_t>(w + ch * 8, g);
+            load8<T>(w + ch * 8, g);
 #pragma unroll
             for (int e = 0; e < 8; ++e) f[e] = (v[i][e] * r) * g[e];
-            store8<bf16_t>(yr + ch * 8, f);
+            store8<T>(yr + ch * 8, f);
         }
     }
 }
 
-// ---- out[i] = table[clamp(ids[i])] (+ pos[i % L]) in fp32; one workgroup per token
+// ---- out[i] = table[clamp(ids[i])] (+ pos[i % L]) in fp32; one workgroup per token (T: element type of the tables)
+template <typename T>
 __global__ void __launch_bounds__(256)
-text_embed_kernel(const int64_t* __restrict__ ids, const bf16_t* __restrict__ table, int64_t vocab, int D,
-                  const bf16_t* __restrict__ pos, int64_t L, float* __restrict__ out, int64_t ldo) {
+text_embed_kernel(const int64_t* __restrict__ ids, const T* __restrict__ table, int64_t vocab, int D,
+                  const T* __restrict__ pos, int64_t L, float* __restrict__ out, int64_t ldo) {
     const int64_t i = blockIdx.x;
     int64_t id = ids[i];
     id = id < 0 ? 0 : id >= vocab ? vocab - 1 : id;              // a bad id never becomes an address outside the table
-    const bf16_t* const tr = table + id * D;
-    const bf16_t* const pr = pos ? pos + (i % L) * D : nullptr;
+    const T* const tr = table + id * D;
+    const T* const pr = pos ? pos + (i % L) * D : nullptr;
     float* const orow = out + i * ldo;
     for (int ch = threadIdx.x; ch < (D >> 3); ch += 256) {
         float f[8];
-        load8<bf16_t>(tr + ch * 8, f);
+        load8<T>(tr + ch * 8, f);
         if (pr) {
             float g[8];
-            load8<bf16_t>(pr + ch * 8, g);
+            load8<T>(pr + ch * 8, g);
 #pragma unroll
             for (int e = 0; e < 8; ++e) f[e] += g[e];
         }
@@ -242,36 +247,157 @@ template <int KIND> DWM_DEVINL float text_act_f(float x) {
     return x / (1.f + __builtin_amdgcn_exp2f(-z));
 }
 
-template <int KIND, bool GATED>
+// The fp32 accuracy path: the same three formulations on the library's exp / erfc / log (about an ulp each) instead of the hardware
+// exp2 / log2 approximations, in the natural-log domain.  Kind 2: t = 2 sqrt(2 / pi) (x + 0.044715 x^3); below t = -20 the 1 of
+// 1 + e^-t is under half an ulp of e^-t, and x e^t = -e^(t + ln |x|) is formed in the exponent, where a subnormal sigmoid cannot
+// cost the product its precision
+template <int KIND> DWM_DEVINL float text_act_f32_f(float x) {
+    if (KIND == 0) return x / (1.f + expf(-1.702f * x));
+    if (KIND == 1) return 0.5f * x * erfcf(-0.7071067811865476f * x);
+    const float t = x * (1.5957691216057308f + 0.07135481627260025f * x * x);
+    if (t < -20.f) return -expf(t + logf(-x));
+    return x / (1.f + expf(-t));
+}
+template <int KIND, typename T> DWM_DEVINL float text_act_of(float x) {
+    if constexpr (std::is_same<T, float>::value) return text_act_f32_f<KIND>(x);
+    else return text_act_f<KIND>(x);
+}
+
+template <int KIND, bool GATED, typename T>
 __global__ void __launch_bounds__(256)
-text_act_kernel(const bf16_t* __restrict__ x, int64_t ldx, int64_t rows, int nch, bf16_t* __restrict__ y, int64_t ldy) {
+text_act_kernel(const T* __restrict__ x, int64_t ldx, int64_t rows, int nch, T* __restrict__ y, int64_t ldy) {
     const int64_t total = rows * nch;
     for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
         const int64_t r = idx / nch;
         const int c = (int)(idx - r * nch) * 8;
         float a[8], f[8];
-        load8<bf16_t>(x + r * ldx + c, a);
+        load8<T>(x + r * ldx + c, a);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) f[e] = text_act_f<KIND>(a[e]);
+        for (int e = 0; e < 8; ++e) f[e] = text_act_of<KIND, T>(a[e]);
         if (GATED) {
             float g[8];
-            load8<bf16_t>(x + r * ldx + (int64_t)nch * 8 + c, g);
+            load8<T>(x + r * ldx + (int64_t)nch * 8 + c, g);
 #pragma unroll
             for (int e = 0; e < 8; ++e) f[e] *= g[e];
         }
-        store8<bf16_t>(y + r * ldy + c, f);
+        store8<T>(y + r * ldy + c, f);
     }
 }
 
-template <int KIND>
+template <int KIND, typename T>
 int text_act_launch(const void* x, int64_t ldx, int64_t rows, int nch, int gated, void* y, int64_t ldy, hipStream_t st) {
     const int64_t total = rows * nch;
     const unsigned grid = (unsigned)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
     if (gated)
-        hipLaunchKernelGGL((text_act_kernel<KIND, true>), dim3(grid), dim3(256), 0, st, (const bf16_t*)x, ldx, rows, nch, (bf16_t*)y, ldy);
+        hipLaunchKernelGGL((text_act_kernel<KIND, true, T>), dim3(grid), dim3(256), 0, st, (const T*)x, ldx, rows, nch, (T*)y, ldy);
     else
-        hipLaunchKernelGGL((text_act_kernel<KIND, false>), dim3(grid), dim3(256), 0, st, (const bf16_t*)x, ldx, rows, nch, (bf16_t*)y, ldy);
+        hipLaunchKernelGGL((text_act_kernel<KIND, false, T>), dim3(grid), dim3(256), 0, st, (const T*)x, ldx, rows, nch, (T*)y, ldy);
     return dwm_launch_status();
+}
+
+// what dwm_text_act and dwm_text_act_f32 share; T: bf16_t or float, 16 / sizeof(T) elements per 16 bytes
+template <typename T>
+int text_act_entry(const void* x, int64_t ldx, int64_t rows, int64_t F, int32_t kind, int32_t gated, void* y, int64_t ldy, void* stream) {
+    constexpr int64_t V = 16 / sizeof(T);
+    if (x == nullptr || y == nullptr || rows <= 0 || F <= 0 || kind < 0 || kind > 2 || (gated != 0 && gated != 1)) return DWM_EINVAL;
+    if (F % 8 != 0 || F >= (1ll << 31)) return DWM_EUNSUPPORTED;
+    if (ldx < (gated ? 2 * F : F) || ldy < F) return DWM_EINVAL;
+    if (ldx % V != 0 || ldy % V != 0 || !dwm_aligned16(x) || !dwm_aligned16(y)) return DWM_EALIGN;
+    const int nch = (int)(F / 8);
+    hipStream_t st = (hipStream_t)stream;
+    if (kind == 0) return text_act_launch<0, T>(x, ldx, rows, nch, gated, y, ldy, st);
+    if (kind == 1) return text_act_launch<1, T>(x, ldx, rows, nch, gated, y, ldy, st);
+    return text_act_launch<2, T>(x, ldx, rows, nch, gated, y, ldy, st);
+}
+
+// ---- fp32 attention (dwm_text_attention_f32).  One head's K and V in fp32 are 64 KiB, so the bf16 plan (a wave owns a head, four
+// heads per workgroup) does not fit 160 KiB of LDS: here ONE WORKGROUP of 4 waves owns a (sequence, head), stages its K rows
+// ([L][64] fp32, row pitch 65 words: lane l reading row l at column d hits bank (l + d) % 64, conflict-free) and V rows ([L][64],
+// pitch 64: lane = channel) once, and its waves take the queries round-robin.  Per query, in a wave:
+//   scores: lane l owns keys l and l + 64; s = sum_d q[d] k[d] as a chain of 64 fp32 FMAs, d ascending (q read from a per-wave LDS
+//     row, a broadcast); x = scale s + bias in fp32; excluded keys (>= L, causally hidden) by selection, their K row address
+//     clamped to L - 1;
+//   softmax: exact maximum and sum over the wave (xor trees: a fixed order), p = expf(x - m), 0 for an excluded key;
+//   output: lane d owns channel d; o = sum_j p[j] V[j][d] as a chain of fp32 FMAs over the visible keys, j ascending (p through a
+//     per-wave LDS row), then ONE division by the sum.  Nothing is rounded to bf16 anywhere.
+// Every wave walks ceil(L / 4) queries (the barriers are uniform); a query >= L repeats row L - 1 and is not stored.
+constexpr int TF_KPITCH = 65;
+constexpr int TF_LDS = (128 * TF_KPITCH + 128 * 64 + 4 * 64 + 4 * 128) * 4;      // 69120 B: two workgroups per CU
+
+struct TfParams {
+    const float *q, *k, *v;
+    float* o;
+    const float* bias;
+    int64_t ld, ldo;
+    int L, heads, causal;
+    float scale;
+};
+
+__global__ void __launch_bounds__(256)
+text_attn_f32_kernel(const TfParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int64_t seq = (int64_t)blockIdx.x / p.heads;
+    const int h = (int)((int64_t)blockIdx.x - seq * p.heads);
+    const int L = p.L;
+    const int64_t row0 = seq * L;
+    float* const Ks = (float*)smem;
+    float* const Vs = Ks + 128 * TF_KPITCH;
+    float* const qs = Vs + 128 * 64 + wave * 64;
+    float* const ps = Vs + 128 * 64 + 4 * 64 + wave * 128;
+    const float* const qg = p.q + h * 64;
+    const float* const kg = p.k + h * 64;
+    const float* const vg = p.v + h * 64;
+
+    for (int idx = tid; idx < L * 16; idx += 256) {              // rows 0 .. L - 1, 16 chunks of 16 bytes each
+        const int r = idx >> 4, c = (idx & 15) * 4;
+        const float4 kk = *(const float4*)(kg + (row0 + r) * p.ld + c);
+        const float4 vv = *(const float4*)(vg + (row0 + r) * p.ld + c);
+        float* const kd = Ks + r * TF_KPITCH + c;
+        kd[0] = kk.x; kd[1] = kk.y; kd[2] = kk.z; kd[3] = kk.w;
+        *(float4*)(Vs + r * 64 + c) = vv;
+    }
+    __syncthreads();
+
+    const int kr0 = lane < L ? lane : L - 1, kr1 = lane + 64 < L ? lane + 64 : L - 1;
+    const float* const k0 = Ks + kr0 * TF_KPITCH;
+    const float* const k1 = Ks + kr1 * TF_KPITCH;
+    for (int q0 = 0; q0 < L; q0 += 4) {
+        const int iq = q0 + wave;
+        const int iqc = iq < L ? iq : L - 1;
+        qs[lane] = qg[(row0 + iqc) * p.ld + lane];
+        __syncthreads();
+        float s0 = 0.f, s1 = 0.f;
+#pragma unroll 16
+        for (int d = 0; d < 64; ++d) {
+            const float qd = qs[d];
+            s0 = fmaf(qd, k0[d], s0);
+            s1 = fmaf(qd, k1[d], s1);
+        }
+        float x0 = s0 * p.scale, x1 = s1 * p.scale;
+        if (p.bias) {
+            const float* const brow = p.bias + ((int64_t)h * L + iqc) * L;
+            x0 += brow[kr0];
+            x1 += brow[kr1];
+        }
+        const bool live0 = lane < L && (!p.causal || lane <= iqc);
+        const bool live1 = lane + 64 < L && (!p.causal || lane + 64 <= iqc);
+        float mx = fmaxf(live0 ? x0 : -INFINITY, live1 ? x1 : -INFINITY);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));      // finite: key 0 is live for every query
+        const float p0 = live0 ? expf(x0 - mx) : 0.f;            // selection: an excluded key contributes exactly 0
+        const float p1 = live1 ? expf(x1 - mx) : 0.f;
+        const float sum = wave_sum(p0 + p1);
+        ps[lane] = p0;
+        ps[lane + 64] = p1;
+        __syncthreads();
+        const int nk = p.causal ? iqc + 1 : L;
+        float acc = 0.f;
+        for (int j = 0; j < nk; ++j) acc = fmaf(ps[j], Vs[j * 64 + lane], acc);
+        if (iq < L) p.o[(row0 + iq) * p.ldo + h * 64 + lane] = acc / sum;
+    }
 }
 
 }  // namespace
@@ -307,7 +433,7 @@ extern "C" int dwm_rmsnorm_rows(const float* x, int64_t ldx, int64_t rows, int64
     if (ldx < D || ldy < D) return DWM_EINVAL;
     if (ldx % 4 != 0 || ldy % 8 != 0 || !dwm_aligned16(x) || !dwm_aligned16(w) || !dwm_aligned16(y)) return DWM_EALIGN;
     if (rows >= (1ll << 31)) return DWM_EUNSUPPORTED;
-    hipLaunchKernelGGL(rmsnorm_rows_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, x, ldx, (int)D, (const bf16_t*)w, eps,
+    hipLaunchKernelGGL(rmsnorm_rows_kernel<bf16_t>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, x, ldx, (int)D, (const bf16_t*)w, eps,
                        (bf16_t*)y, ldy);
     return dwm_launch_status();
 }
@@ -322,20 +448,66 @@ extern "C" int dwm_text_embed(const int64_t* ids, int64_t n, const void* table, 
         (((uintptr_t)ids) & 7u) != 0)
         return DWM_EALIGN;
     if (n >= (1ll << 31)) return DWM_EUNSUPPORTED;
-    hipLaunchKernelGGL(text_embed_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, ids, (const bf16_t*)table, vocab, (int)D,
+    hipLaunchKernelGGL(text_embed_kernel<bf16_t>, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, ids, (const bf16_t*)table, vocab, (int)D,
                        (const bf16_t*)pos, pos != nullptr ? L : 1, out, ldo);
     return dwm_launch_status();
 }
 
 extern "C" int dwm_text_act(const void* x, int64_t ldx, int64_t rows, int64_t F, int32_t kind, int32_t gated, void* y, int64_t ldy,
                             void* stream) {
-    if (x == nullptr || y == nullptr || rows <= 0 || F <= 0 || kind < 0 || kind > 2 || (gated != 0 && gated != 1)) return DWM_EINVAL;
-    if (F % 8 != 0 || F >= (1ll << 31)) return DWM_EUNSUPPORTED;
-    if (ldx < (gated ? 2 * F : F) || ldy < F) return DWM_EINVAL;
-    if (ldx % 8 != 0 || ldy % 8 != 0 || !dwm_aligned16(x) || !dwm_aligned16(y)) return DWM_EALIGN;
-    const int nch = (int)(F / 8);
-    hipStream_t st = (hipStream_t)stream;
-    if (kind == 0) return text_act_launch<0>(x, ldx, rows, nch, gated, y, ldy, st);
-    if (kind == 1) return text_act_launch<1>(x, ldx, rows, nch, gated, y, ldy, st);
-    return text_act_launch<2>(x, ldx, rows, nch, gated, y, ldy, st);
+    return text_act_entry<bf16_t>(x, ldx, rows, F, kind, gated, y, ldy, stream);
+}
+
+// ---- the fp32 accuracy path: the same refusals as the bf16 entries, strides in fp32 elements (16 bytes = 4 of them)
+extern "C" int dwm_text_attention_f32(const dwm_text_attn_args* a, void* stream) {
+    if (a == nullptr || a->q == nullptr || a->k == nullptr || a->v == nullptr || a->out == nullptr) return DWM_EINVAL;
+    if (a->L < 1 || a->L > 128) return DWM_EUNSUPPORTED;
+    if (a->n_seq <= 0 || a->heads <= 0 || (a->causal != 0 && a->causal != 1)) return DWM_EINVAL;
+    const int64_t width = (int64_t)a->heads * 64;
+    if (a->ld < width || a->ldo < width) return DWM_EINVAL;
+    if (a->ld % 4 != 0 || a->ldo % 4 != 0) return DWM_EALIGN;
+    if (!dwm_aligned16(a->q) || !dwm_aligned16(a->k) || !dwm_aligned16(a->v) || !dwm_aligned16(a->out)) return DWM_EALIGN;
+    if (a->bias != nullptr && (((uintptr_t)a->bias) & 3u) != 0) return DWM_EALIGN;
+    if (a->heads > (1 << 16) || a->n_seq > (1ll << 31) / a->heads - 1) return DWM_EUNSUPPORTED;      // one-dimensional grid
+    TfParams p;
+    p.q = (const float*)a->q; p.k = (const float*)a->k; p.v = (const float*)a->v; p.o = (float*)a->out;
+    p.bias = a->bias;
+    p.ld = a->ld; p.ldo = a->ldo;
+    p.L = (int)a->L; p.heads = a->heads; p.causal = a->causal;
+    p.scale = a->scale;
+    const hipError_t e = dwm_allow_dynamic_lds<text_attn_f32_kernel>(TF_LDS);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(text_attn_f32_kernel, dim3((unsigned)(a->n_seq * a->heads)), dim3(256), (size_t)TF_LDS, (hipStream_t)stream, p);
+    return dwm_launch_status();
+}
+
+extern "C" int dwm_rmsnorm_rows_f32(const float* x, int64_t ldx, int64_t rows, int64_t D, const float* w, float eps, float* y, int64_t ldy,
+                                    void* stream) {
+    if (x == nullptr || w == nullptr || y == nullptr || rows <= 0 || D <= 0) return DWM_EINVAL;
+    if (D % 8 != 0 || D > 8192) return DWM_EUNSUPPORTED;
+    if (ldx < D || ldy < D) return DWM_EINVAL;
+    if (ldx % 4 != 0 || ldy % 4 != 0 || !dwm_aligned16(x) || !dwm_aligned16(w) || !dwm_aligned16(y)) return DWM_EALIGN;
+    if (rows >= (1ll << 31)) return DWM_EUNSUPPORTED;
+    hipLaunchKernelGGL(rmsnorm_rows_kernel<float>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, x, ldx, (int)D, w, eps, y, ldy);
+    return dwm_launch_status();
+}
+
+extern "C" int dwm_text_embed_f32(const int64_t* ids, int64_t n, const float* table, int64_t vocab, int64_t D, const float* pos, int64_t L,
+                                  float* out, int64_t ldo, void* stream) {
+    if (ids == nullptr || table == nullptr || out == nullptr || n <= 0 || vocab <= 0 || D <= 0) return DWM_EINVAL;
+    if (pos != nullptr && L <= 0) return DWM_EINVAL;
+    if (D % 8 != 0 || D >= (1ll << 31)) return DWM_EUNSUPPORTED;
+    if (ldo < D) return DWM_EINVAL;
+    if (ldo % 4 != 0 || !dwm_aligned16(table) || !dwm_aligned16(out) || (pos != nullptr && !dwm_aligned16(pos)) ||
+        (((uintptr_t)ids) & 7u) != 0)
+        return DWM_EALIGN;
+    if (n >= (1ll << 31)) return DWM_EUNSUPPORTED;
+    hipLaunchKernelGGL(text_embed_kernel<float>, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, ids, table, vocab, (int)D, pos,
+                       pos != nullptr ? L : 1, out, ldo);
+    return dwm_launch_status();
+}
+
+extern "C" int dwm_text_act_f32(const float* x, int64_t ldx, int64_t rows, int64_t F, int32_t kind, int32_t gated, float* y, int64_t ldy,
+                                void* stream) {
+    return text_act_entry<float>(x, ldx, rows, F, kind, gated, y, ldy, stream);
 }

@@ -265,7 +265,8 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
          rms_w: Optional[torch.Tensor] = None, rms_ncols: int = 0, rms_eps: float = 1e-6,
          a_grid=None, conv3x3: bool = False, stride2=False, conv_taps: Optional[list] = None,
          c_grid=None, out32: Optional[torch.Tensor] = None, mirror: bool = True, w_is_activation: bool = False,
-         rows: Optional[int] = None, split_k: int = 0, tile: int = 0, _debug: int = 0) -> torch.Tensor:
+         rows: Optional[int] = None, split_k: int = 0, tile: int = 0, _debug: int = 0,
+         w_planes: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[M, Nout] = epilogue(a[M, K] @ w[N, K]^T).  See dwm_gemm_bf16.
     tile: 0 = the kernel's choice, 1 = 256 x 256 tiles, 2 = 256 x 128 tiles (two workgroups per CU).
     a_grid: A is a padded token grid (PaddedGrid.rows x C); M = its pixel count; with conv3x3 the K
@@ -276,10 +277,15 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
     out32 in fp32 (out32 may be `res` or `blend` itself) and, rounded, to the bf16 `out`; mirror=False: no bf16 copy at all
     (`out` must be None; the call returns out32) - the hidden / context streams of the bf16 MMDiT forward.
     w_is_activation: `w` is a per-call tensor, not a parameter (fp32 path: its operand planes are not cached).
-    fp32 `a`: the accuracy path (dwm_gemm_f32), all operands fp32; out32, mirror, split_k, tile and _debug are not looked at."""
+    fp32 `a`: the accuracy path (dwm_gemm_f32), all operands fp32; out32, mirror, tile and _debug are not looked at, and of split_k
+    only the value 1: it forbids the kernel's own split-K rule, so that a row's sum does not depend on M (the text encoders);
+    w_planes: split_weight(w, cache=False) where the caller holds the planes itself (they are then not looked up in, or added
+    to, the process-wide cache of split_weight)."""
+    if w_planes is not None and a.dtype != f32:
+        raise RuntimeError("gemm: w_planes belongs to the fp32 path")
     if a.dtype == f32:
         return _gemm_f32(a, w, bias, out, rows, epilogue, act, gate, rows_per_gate, res, res_mod, blend, alpha, rows_per_alpha, rms_w,
-                         rms_ncols, rms_eps, a_grid, conv3x3, stride2, conv_taps, c_grid, not w_is_activation)
+                         rms_ncols, rms_eps, a_grid, conv3x3, stride2, conv_taps, c_grid, not w_is_activation, split_k == 1, w_planes)
     M, N, K, _, nout, orow = _gemm_dims(a, w, bf16, rows, epilogue, a_grid, conv3x3, stride2, conv_taps, c_grid, False)
     if not mirror:
         if out32 is None or out is not None:
@@ -576,16 +582,24 @@ def clear_split_weights() -> None:
 
 
 def _gemm_f32(a, w, bias, out, rows, epilogue, act, gate, rows_per_gate, res, res_mod, blend, alpha, rows_per_alpha, rms_w, rms_ncols,
-              rms_eps, a_grid, conv3x3, stride2, conv_taps, c_grid, cache_w):
-    """gemm() for fp32 operands (dwm_gemm_f32)"""
+              rms_eps, a_grid, conv3x3, stride2, conv_taps, c_grid, cache_w, no_split=False, w_planes=None):
+    """gemm() for fp32 operands (dwm_gemm_f32).  no_split: one K range whatever the tile grid (dwm_gemm_args.split_k = 1);
+    w_planes: split_weight(w) held by the caller, used as it is"""
     M, N, K, taps, nout, orow = _gemm_dims(a, w, f32, rows, epilogue, a_grid, conv3x3, stride2, conv_taps, c_grid, True)
     out = _gemm_out(out, (orow, nout), f32, a.device, c_grid is not None)
     _chkvec(bias, "bias", f32)
     # the W operand is the pre-split bf16 planes of w (an activation in the W position - attention scores of the VAE - is not kept)
-    ws = split_weight(w, taps, cache=cache_w)
+    if w_planes is None:
+        ws = split_weight(w, taps, cache=cache_w)
+    else:
+        ws = w_planes
+        _chk2d(ws, "w_planes", bf16)
+        if taps != 1 or tuple(ws.shape) != (N, 3 * K) or not ws.is_contiguous():
+            raise RuntimeError(f"gemm: w_planes must be the contiguous [N, 3K] = [{N}, {3 * K}] planes of a plain GEMM's weight")
     g = _lib.GemmArgs()
     g.A, g.lda, g.W, g.bias, g.C, g.ldc = a.data_ptr(), a.stride(0), ws.data_ptr(), _p(bias), out.data_ptr(), out.stride(0)
     g.M, g.N, g.K, g.epilogue, g.act = M, N, K, epilogue, act
+    g.split_k = 1 if no_split else 0
     _gemm_operands(g, f32, f32, gate, rows_per_gate, res, res_mod, blend, alpha, rows_per_alpha, rms_w, rms_ncols, rms_eps)
     _gemm_maps(g, a, a_grid, conv3x3, stride2, conv_taps, c_grid, res, blend)
     # scratch, grown on demand: the operand planes of A + one set of fp32 partial slices per group of 9 taps
@@ -593,7 +607,7 @@ def _gemm_f32(a, w, bias, out, rows, epilogue, act, gate, rows_per_gate, res, re
     groups = (taps + 8) // 9
     need = 4 * a_rows * (K // taps) + 256 + 4 * M * N * groups
     tiles = ((M + 255) // 256) * ((N + 255) // 256)
-    if tiles * groups <= 128:
+    if tiles * groups <= 128 and not no_split:
         need += 4 * M * N * min(32, 256 // tiles)          # room for the kernel's own split-K rule
     wsb = _f32_workspace(a.device, need)
     g.workspace, g.workspace_bytes = wsb.data_ptr(), wsb.numel() * 4
@@ -1295,7 +1309,9 @@ def text_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch
                    causal: bool = False, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = softmax(scale q k^T [+ bias] [causal]) v for n_seq sequences of L tokens, `heads` heads of width 64 (dwm_text_attention).
     q, k, v: bf16 [n_seq*L, heads*64] with contiguous rows and ONE row stride (column blocks of a fused QKV buffer); bias: fp32
-    [heads, L, L] or None.  L outside 1..TEXT_ATTENTION_MAX_L or another head width: NotImplementedError."""
+    [heads, L, L] or None.  L outside 1..TEXT_ATTENTION_MAX_L or another head width: NotImplementedError.
+    fp32 q: the accuracy path (dwm_text_attention_f32) - k, v and out fp32 too, exact fp32 contractions."""
+    dt = _dt(q)
     if not 1 <= L <= TEXT_ATTENTION_MAX_L:
         raise NotImplementedError(f"text_attention: L = {L} is outside 1..{TEXT_ATTENTION_MAX_L}")
     if heads <= 0 or q.shape[-1] != heads * 64:
@@ -1303,7 +1319,7 @@ def text_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch
     if n_seq <= 0:
         raise RuntimeError(f"text_attention: n_seq must be positive, got {n_seq}")
     for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
-        _chk2d(t, name)
+        _chk2d(t, name, dt)
         if tuple(t.shape) != (n_seq * L, heads * 64):
             raise RuntimeError(f"text_attention: {name} must be [n_seq*L, heads*64] = [{n_seq * L}, {heads * 64}], got {tuple(t.shape)}")
     if not (q.stride(0) == k.stride(0) == v.stride(0)):
@@ -1316,32 +1332,35 @@ def text_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch
     a = _lib.TextAttnArgs()
     a.q, a.k, a.v, a.ld, a.out, a.ldo = q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(0), out.data_ptr(), out.stride(0)
     a.n_seq, a.L, a.heads, a.scale, a.causal, a.bias = n_seq, L, heads, float(scale), int(bool(causal)), _p(bias)
-    _call("dwm_text_attention", C.byref(a))
+    _call("dwm_text_attention_f32" if dt == f32 else "dwm_text_attention", C.byref(a))
     return out
 
 
 def rmsnorm_rows(x: torch.Tensor, weight: torch.Tensor, eps: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """T5LayerNorm of the fp32 residual stream x [rows, D] -> bf16 (dwm_rmsnorm_rows): x rsqrt(mean(x^2) + eps) weight"""
+    """T5LayerNorm of the fp32 residual stream x [rows, D] -> bf16 (dwm_rmsnorm_rows): x rsqrt(mean(x^2) + eps) weight.
+    fp32 weight: the accuracy path (dwm_rmsnorm_rows_f32), fp32 out"""
+    dt = _dt(weight)
     _chk2d(x, "x", f32)
-    _chkvec(weight, "weight")
+    _chkvec(weight, "weight", dt)
     rows, D = x.shape
     if weight.numel() != D:
         raise RuntimeError(f"rmsnorm_rows: weight must have {D} elements, got {weight.numel()}")
     if D % 8 != 0 or D > 8192:
         raise NotImplementedError(f"rmsnorm_rows: D = {D} must be a multiple of 8, at most 8192")
     if out is None:
-        out = torch.empty((rows, D), dtype=bf16, device=x.device)
-    _chk2d(out, "out")
+        out = torch.empty((rows, D), dtype=dt, device=x.device)
+    _chk2d(out, "out", dt)
     if out.shape != x.shape:
         raise RuntimeError("rmsnorm_rows: out must have the shape of x")
-    _call("dwm_rmsnorm_rows", x.data_ptr(), x.stride(0), rows, D, weight.data_ptr(), float(eps), out.data_ptr(), out.stride(0))
+    _call("dwm_rmsnorm_rows_f32" if dt == f32 else "dwm_rmsnorm_rows", x.data_ptr(), x.stride(0), rows, D, weight.data_ptr(), float(eps),
+          out.data_ptr(), out.stride(0))
     return out
 
 
 def text_embed(ids: torch.Tensor, table: torch.Tensor, pos: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fp32 stream [n_seq*L, D] = table[ids] (+ pos[position]) for ids [n_seq, L] int64 (dwm_text_embed).  Ids that arrive on the
     host - the normal case: the tokenizer runs there - are checked against the vocabulary here; ids already on the device are
-    clamped by the kernel instead (checking them would cost a synchronisation)."""
+    clamped by the kernel instead (checking them would cost a synchronisation).  fp32 table (and pos): dwm_text_embed_f32."""
     if ids.dim() != 2 or ids.dtype != torch.int64:
         raise RuntimeError(f"text_embed: ids must be a 2-D int64 tensor, got {tuple(ids.shape)} {ids.dtype}")
     if table.dim() != 2 or ids.numel() == 0:
@@ -1350,12 +1369,13 @@ def text_embed(ids: torch.Tensor, table: torch.Tensor, pos: Optional[torch.Tenso
     n_seq, L = ids.shape
     if not ids.is_cuda and (int(ids.min()) < 0 or int(ids.max()) >= vocab):
         raise ValueError(f"text_embed: token ids outside [0, {vocab}): min {int(ids.min())}, max {int(ids.max())}")
-    _chk2d(table, "table")
+    dt = _dt(table)
+    _chk2d(table, "table", dt)
     ids = ids.to(table.device)
     if not table.is_contiguous() or D % 8 != 0:
         raise RuntimeError("text_embed: the table must be contiguous with D % 8 == 0")
     if pos is not None:
-        _chk2d(pos, "pos")
+        _chk2d(pos, "pos", dt)
         if not pos.is_contiguous() or pos.shape[1] != D or pos.shape[0] < L:
             raise RuntimeError(f"text_embed: pos must be a contiguous [>= {L}, {D}] table, got {tuple(pos.shape)}")
     ids = ids.contiguous()
@@ -1364,26 +1384,28 @@ def text_embed(ids: torch.Tensor, table: torch.Tensor, pos: Optional[torch.Tenso
     _chk2d(out, "out", f32)
     if tuple(out.shape) != (n_seq * L, D):
         raise RuntimeError("text_embed: out must be [n_seq*L, D]")
-    _call("dwm_text_embed", ids.data_ptr(), n_seq * L, table.data_ptr(), vocab, D, _p(pos), L, out.data_ptr(), out.stride(0))
+    _call("dwm_text_embed_f32" if dt == f32 else "dwm_text_embed", ids.data_ptr(), n_seq * L, table.data_ptr(), vocab, D, _p(pos), L, out.data_ptr(), out.stride(0))
     return out
 
 
 def text_act(x: torch.Tensor, kind: str, gated: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """act(x) (x [rows, F]) or act(x[:, :F]) * x[:, F:] (gated, x [rows, 2F]) on bf16, computed in fp32 (dwm_text_act);
-    kind: a key of TEXT_ACT_KINDS (the transformers activation names)"""
+    kind: a key of TEXT_ACT_KINDS (the transformers activation names).  fp32 x: the accuracy path (dwm_text_act_f32), fp32 out,
+    the library's exp / erfc instead of the hardware approximations"""
     if kind not in TEXT_ACT_KINDS:
         raise NotImplementedError(f"text_act: activation {kind!r} is not one of {sorted(TEXT_ACT_KINDS)}")
-    _chk2d(x, "x")
+    dt = _dt(x)
+    _chk2d(x, "x", dt)
     rows, cols = x.shape
     F = cols // 2 if gated else cols
     if (gated and cols % 2) or F % 8 != 0:
         raise RuntimeError(f"text_act: {cols} columns do not make {'2 x ' if gated else ''}F with F % 8 == 0")
     if out is None:
-        out = torch.empty((rows, F), dtype=bf16, device=x.device)
-    _chk2d(out, "out")
+        out = torch.empty((rows, F), dtype=dt, device=x.device)
+    _chk2d(out, "out", dt)
     if tuple(out.shape) != (rows, F):
         raise RuntimeError("text_act: out must be [rows, F]")
-    _call("dwm_text_act", x.data_ptr(), x.stride(0), rows, F, TEXT_ACT_KINDS[kind], int(bool(gated)), out.data_ptr(), out.stride(0))
+    _call("dwm_text_act_f32" if dt == f32 else "dwm_text_act", x.data_ptr(), x.stride(0), rows, F, TEXT_ACT_KINDS[kind], int(bool(gated)), out.data_ptr(), out.stride(0))
     return out
 
 

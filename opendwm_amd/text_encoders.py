@@ -20,9 +20,20 @@ split_k = 1, so a row's result does not depend on how many rows the call has: en
 (`SD3TextEncoders.encode(dedupe=True)`) is bit-equal to encoding every copy.  There is no PyTorch fallback: tensors off the device,
 another head width, L > 128 or an activation the kernels do not have raise.
 
+THE FP32 ACCURACY PATH: `model.to(device).to(torch.float32)` - the reference's `torch_dtype` load argument - selects
+it for all three classes: fp32 weights, activations and residual stream, fp32 outputs.  Every linear layer is ops.gemm on fp32
+operands (dwm_gemm_f32, split_k = 1 so that the row-independence above holds; the stream updates are its RESID epilogue in place),
+CLIP's norms ops.layernorm on fp32, and rmsnorm_rows / text_attention / text_embed / text_act take their fp32 forms (exact fp32
+contractions in the attention, library exp / erfc in the activations).  The pre-split bf16 planes of each GEMM operand
+(ops.split_weight: 6 bytes per weight beside the 4 of the fp32 weight itself) are made where the operands are packed and are HELD BY
+THE MODEL, in the same `_packed` entry, released with it by `.to()` / `load_state_dict`; they never enter the process-wide cache of
+split_weight.  `.to(torch.bfloat16)` on the same object gives the bf16 model again, bit-equal to a freshly loaded one.
+`quantization_config` is a bf16 feature: together with fp32 the forward raises NotImplementedError.  Other dtypes, and any model off
+the device, raise RuntimeError.
+
 TOKENISATION STAYS WITH THE CALLER: the tokenizers are host string code and no vocabulary files ship with this package; every
 entry point here takes token ids (int64 [N, L], normally still on the host, where they are checked against the vocabulary).
-Out of scope: an fp32 accuracy path, training (the encoders are frozen in the reference), L > 128, HIP-graph capture.
+Out of scope: training (the encoders are frozen in the reference), L > 128, HIP-graph capture, NF4 in fp32.
 
 4-BIT WEIGHTS (`quantization_config`): all three classes take the dict the reference's example configs pass as
 `text_encoder_load_args.quantization_config` (the key names of transformers.BitsAndBytesConfig; an object with `to_dict()` is
@@ -57,6 +68,7 @@ from . import ops
 from ._lib import EPI_RESID
 
 bf16 = torch.bfloat16
+f32 = torch.float32
 
 
 class TextEncoderOutput:
@@ -143,6 +155,14 @@ class _Nf4Weight:
         self.numel = self.shape[0] * self.shape[1]
 
 
+class _F32Weight:
+    """one GEMM operand of the fp32 path: the fp32 weight [N, K] and its pre-split bf16 planes [N, 3K] (ops.split_weight), which
+    live exactly as long as the model's `_packed` entry that holds this object"""
+
+    def __init__(self, w: torch.Tensor):
+        self.w, self.planes = w, ops.split_weight(w, cache=False)
+
+
 class _Frozen(nn.Module):
     """what the three classes share: config, `.device` / `.dtype`, the packed-operand cache and its invalidation, 4-bit weights"""
     NF4_DEFAULT_SKIP: Tuple[str, ...] = ()
@@ -204,6 +224,8 @@ class _Frozen(nn.Module):
         views of it), as bf16 - or, where the configuration says so, quantised, the bf16 storage released"""
         mods = [self.get_submodule(n) for n in names]
         w = self._pack([m.weight for m in mods]) if len(mods) > 1 else mods[0].weight.data
+        if w.dtype == f32:                              # the accuracy path (quantisation was refused by _ids)
+            return _F32Weight(w)
         if not self._wants_nf4(names):
             return w
         q, absmax = ops.nf4_quantize(w.contiguous())
@@ -238,7 +260,12 @@ class _Frozen(nn.Module):
 
     def _linear(self, x, op, bias=None, h=None):
         """x op^T (+ bias) -> bf16, or added in place into the fp32 residual stream h (which is returned).  op: a bf16 weight - the
-        launches of the unquantised model - or an _Nf4Weight on the model's route"""
+        launches of the unquantised model - or an _Nf4Weight on the model's route; an _F32Weight: the same in fp32, x and the
+        result fp32 (dwm_gemm_f32 on the planes the operand holds, never split over K)"""
+        if isinstance(op, _F32Weight):
+            if h is None:
+                return ops.gemm(x, op.w, bias, split_k=1, w_planes=op.planes)
+            return ops.gemm(x, op.w, bias, epilogue=EPI_RESID, res=h, out=h, split_k=1, w_planes=op.planes)
         if isinstance(op, _Nf4Weight):
             if self.quantization["route"] == "fused":
                 return ops.gemm_nf4(x, op.q, op.absmax, bias, out32=h)
@@ -263,9 +290,32 @@ class _Frozen(nn.Module):
     def _ids(self, input_ids):
         if input_ids.dim() != 2:
             raise RuntimeError(f"input_ids must be [N, L], got {tuple(input_ids.shape)}")
-        if self.dtype != bf16 or self.device.type != "cuda":
-            raise RuntimeError("the text encoders run in bf16 on the HIP device (model.to(device).to(torch.bfloat16)); there is no fallback")
+        if self.dtype not in (bf16, f32) or self.device.type != "cuda":
+            raise RuntimeError("the text encoders run in bf16, or in fp32 (the accuracy path), on the HIP device "
+                               "(model.to(device).to(torch.bfloat16) or .to(torch.float32)); there is no fallback")
+        if self.dtype == f32 and self.quantization is not None:
+            raise NotImplementedError("quantization_config (4-bit NF4 weights) together with torch.float32 is not built: quantisation is "
+                                      "a bf16 feature - use .to(torch.bfloat16), or quantization_config=None for the fp32 accuracy path")
         return input_ids.to(torch.int64)
+
+    def _snapshot(self, h):
+        """the residual stream as an entry of `hidden_states`, in the model's dtype"""
+        return h.clone() if self.dtype == f32 else ops.cast_bf16(h)
+
+    def held_bytes(self) -> int:
+        """bytes of device memory this model holds: parameters and buffers, and what `_packed` holds beside them (after a forward:
+        the operand planes of the fp32 path, the scratch buffer of the NF4 "dequant" route)"""
+        def walk(x):
+            if isinstance(x, torch.Tensor):
+                yield x
+            elif isinstance(x, (_F32Weight, _Nf4Weight)):
+                yield from walk(list(vars(x).values()))
+            elif isinstance(x, (list, tuple, dict)):
+                for y in (x.values() if isinstance(x, dict) else x):
+                    yield from walk(y)
+        storages = {t.untyped_storage().data_ptr(): t.untyped_storage().nbytes()
+                    for t in walk([list(self.parameters()), list(self.buffers()), self._packed])}
+        return sum(storages.values())
 
 
 # ------------------------------------------------------------------------------------------------------------------- CLIP
@@ -361,7 +411,7 @@ class CLIPTextModel(_Frozen):
 
     @torch.no_grad()
     def _encode(self, input_ids, output_hidden_states):
-        """(last_hidden_state [N, L, D] bf16, pooled [N, D] bf16, hidden_states or None)"""
+        """(last_hidden_state [N, L, D], pooled [N, D], hidden_states or None), in the model's dtype"""
         ids = self._ids(input_ids)
         c, tm = self.config, self.text_model
         N, L = ids.shape
@@ -370,19 +420,20 @@ class CLIPTextModel(_Frozen):
             raise RuntimeError(f"{L} tokens exceed max_position_embeddings = {c['max_position_embeddings']}")
         pooled_at = eos_positions(ids, c["eos_token_id"]).to(self.device) + torch.arange(N, device=self.device) * L
         h = ops.text_embed(ids, tm.embeddings.token_embedding.weight, tm.embeddings.position_embedding.weight)
-        states = [ops.cast_bf16(h).view(N, L, D)] if output_hidden_states else None
-        ao = torch.empty((N * L, D), dtype=bf16, device=self.device)
+        x32 = self.dtype == bf16                   # bf16: the fp32 stream into bf16 norms; fp32: dwm_layernorm_f32
+        states = [self._snapshot(h).view(N, L, D)] if output_hidden_states else None
+        ao = torch.empty((N * L, D), dtype=self.dtype, device=self.device)
         for l, (wqkv, bqkv, wout, wfc1, wfc2) in zip(tm.encoder.layers, self._operands()["qkv"]):
-            y = ops.layernorm(h, eps=eps, weight=l.layer_norm1.weight, bias=l.layer_norm1.bias, x32=True)
+            y = ops.layernorm(h, eps=eps, weight=l.layer_norm1.weight, bias=l.layer_norm1.bias, x32=x32)
             qkv = self._linear(y, wqkv, bqkv)
             ops.text_attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], ao, N, L, H, 0.125, causal=True)
             self._linear(ao, wout, l.self_attn.out_proj.bias, h)
-            y = ops.layernorm(h, eps=eps, weight=l.layer_norm2.weight, bias=l.layer_norm2.bias, x32=True, out=y)
+            y = ops.layernorm(h, eps=eps, weight=l.layer_norm2.weight, bias=l.layer_norm2.bias, x32=x32, out=y)
             f = ops.text_act(self._linear(y, wfc1, l.mlp.fc1.bias), c["hidden_act"])
             self._linear(f, wfc2, l.mlp.fc2.bias, h)
             if output_hidden_states:
-                states.append(ops.cast_bf16(h).view(N, L, D))
-        last = ops.layernorm(h, eps=eps, weight=tm.final_layer_norm.weight, bias=tm.final_layer_norm.bias, x32=True)
+                states.append(self._snapshot(h).view(N, L, D))
+        last = ops.layernorm(h, eps=eps, weight=tm.final_layer_norm.weight, bias=tm.final_layer_norm.bias, x32=x32)
         pooled = last.index_select(0, pooled_at)
         return last.view(N, L, D), pooled, (tuple(states) if output_hidden_states else None)
 
@@ -535,12 +586,12 @@ class T5EncoderModel(_Frozen):
         inner = 64 * H
         bias = self.relative_bias(L)
         h = ops.text_embed(ids, self.shared.weight)
-        states = [ops.cast_bf16(h).view(N, L, D)] if output_hidden_states else None
-        ao = torch.empty((N * L, inner), dtype=bf16, device=self.device)
-        y = torch.empty((N * L, D), dtype=bf16, device=self.device)
+        states = [self._snapshot(h).view(N, L, D)] if output_hidden_states else None
+        ao = torch.empty((N * L, inner), dtype=self.dtype, device=self.device)
+        y = torch.empty((N * L, D), dtype=self.dtype, device=self.device)
         for i, (b, (wqkv, wo_attn, wi, wo)) in enumerate(zip(self.encoder.block, self._operands()["blocks"])):
             if output_hidden_states and i > 0:
-                states.append(ops.cast_bf16(h).view(N, L, D))
+                states.append(self._snapshot(h).view(N, L, D))
             ops.rmsnorm_rows(h, b.layer[0].layer_norm.weight, eps, out=y)
             qkv = self._linear(y, wqkv)
             ops.text_attention(qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:], ao, N, L, H, 1.0, bias=bias)
