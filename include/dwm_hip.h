@@ -905,6 +905,54 @@ typedef struct dwm_gemm_nf4_args {
 } dwm_gemm_nf4_args;
 int dwm_gemm_nf4(const dwm_gemm_nf4_args* args, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Low-rank adapters (opendwm_amd/lora.py, csrc/lora.hip; DESIGN s26).  An adapted weight is W + scale * B A with W [N, K], A [r, K]
+ * and B [N, r] (A, B, scale fp32).  Both entry points run over a LIST of weights.  `items` is the list in HOST memory (the shapes
+ * are checked there, before anything is launched), `dev_items` the same bytes in DEVICE memory (what the kernels read); every
+ * table is a device array with the meaning it has for dwm_adamw_multi: workgroup b works on item block_item[b], at block_start[b].
+ *   1 <= r <= 64 and K % 4 == 0, else DWM_EUNSUPPORTED; null pointers, N / K / r <= 0, a table whose block count is not the one
+ *   the shapes give: DWM_EINVAL; w / a / out / out2 / ws off 16 bytes, b off 4 bytes: DWM_EALIGN.  Tensors are contiguous.
+ * No atomics in either; every output element has one fixed order of operations, so two launches give equal bits. */
+typedef struct dwm_lora_item {
+    const void* w;          /* merge: W [N, K]; project: G [N, K], the gradient of the adapted weight */
+    const float* a;         /* A [r, K] */
+    const float* b;         /* B [N, r] */
+    void* out;              /* merge: out [N, K] (may be w itself); project: dA [r, K] fp32 */
+    float* out2;            /* project: dB [N, r]; merge: not read */
+    float* ws;              /* project: dwm_lora_project_ws_floats(N, K, r) floats of scratch, need not be initialised; merge: not read */
+    int64_t N, K;
+    int32_t r;
+    int32_t flags;          /* bit 0: w is bf16 (else fp32); bit 1: out is bf16 (else fp32; merge only) */
+    float scale;
+    int32_t reserved;
+    int64_t n;              /* r * K */
+} dwm_lora_item;
+
+/* out[n, k] for every item.  NORMATIVE arithmetic per element, all in fp32:
+ *     acc = 0;  for j = 0 .. r - 1 in this order: acc = fmaf(B[n, j], A[j, k], acc)
+ *     v = fmaf(scale, acc, float(W[n, k]))
+ *     out = v (fp32 out: the fold) or bf16_rne(v) (bf16 out: the merge; the rounding of dwm_cast_f32_to_bf16)
+ * so B == 0 gives the bits dwm_cast_f32_to_bf16 gives W (but for W == -0.0, which becomes +0.0), and the bf16 rounding of the
+ * fold is the merge.  Workgroup b owns the 32-row x 128-column tile block_start[b] of its item, tiles numbered row-major over
+ * ceil(N / 32) x ceil(K / 128); n_blocks = the sum of the tile counts. */
+int dwm_lora_merge_multi(const dwm_lora_item* items, int64_t n_items, const dwm_lora_item* dev_items, const int32_t* block_item,
+                         const int64_t* block_start, int64_t n_blocks, void* stream);
+
+/* dA (+)= scale * B^T G and dB (+)= scale * G A^T for every item (accumulate != 0: added to what dA / dB hold, else they are
+ * overwritten).  G fp32 or bf16 (flags bit 0).  Three launches, G is read twice:
+ *   dA  workgroup b of the da table owns tile block_start[b] of ceil(N / 512) x ceil(K / 128) (row chunk major) and writes
+ *       P[c][j][k] = sum over the chunk's rows n ASCENDING of fmaf(B[n, j], G[n, k], .) into ws [chunks, r, K];
+ *       the fin table cuts the r * K elements of dA into runs of fin_chunk (a multiple of 1024): t = (P[0] + P[1]) + ... ascending,
+ *       dA = scale * t, or fmaf(scale, t, dA) when accumulating.
+ *   dB  workgroup b of the db table owns the 32 rows block_start[b] * 32 ... of its item: t[n][j] = sum over k ASCENDING of
+ *       fmaf(G[n, k], A[j, k], .), dB = scale * t or fmaf(scale, t, dB). */
+int64_t dwm_lora_project_ws_floats(int64_t N, int64_t K, int32_t r);
+int dwm_lora_project_multi(const dwm_lora_item* items, int64_t n_items, const dwm_lora_item* dev_items,
+                           const int32_t* da_block_item, const int64_t* da_block_start, int64_t da_blocks,
+                           const int32_t* fin_block_item, const int64_t* fin_block_start, int64_t fin_blocks, int64_t fin_chunk,
+                           const int32_t* db_block_item, const int64_t* db_block_start, int64_t db_blocks,
+                           int32_t accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,6 +136,11 @@ class GemmNf4Args(C.Structure):
                 ("C32", _vp), ("ldc32", _i64), ("M", _i64), ("N", _i64), ("K", _i64)]
 
 
+class LoraItem(C.Structure):            # one row of the item arrays train_ops.lora_merge_multi / lora_project_multi build (11 x 8 bytes)
+    _fields_ = [("w", _vp), ("a", _vp), ("b", _vp), ("out", _vp), ("out2", _vp), ("ws", _vp), ("N", _i64), ("K", _i64), ("r", _i32),
+                ("flags", _i32), ("scale", _f32), ("reserved", _i32), ("n", _i64)]
+
+
 # name -> (restype, argtypes); every symbol include/dwm_hip.h declares
 SIGNATURES = {
     "dwm_abi_version": (_i32, []),
@@ -254,6 +259,10 @@ SIGNATURES = {
     "dwm_nf4_quantize": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "dwm_nf4_dequantize": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
     "dwm_gemm_nf4": (_i32, [C.POINTER(GemmNf4Args), _vp]),
+    # low-rank adapters: (host items, count, device items), then (block_item, block_start, blocks) per launch
+    "dwm_lora_merge_multi": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "dwm_lora_project_ws_floats": (_i64, [_i64, _i64, _i32]),
+    "dwm_lora_project_multi": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i32, _vp]),
 }
 
 _ERR = {-1: "DWM_EINVAL (bad shape / null pointer)", -2: "DWM_EALIGN (alignment)",

@@ -17,7 +17,7 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libdwm_hip.so")
 SOURCES = ["gemm_bf16.hip", "gemm_bf16_4w.hip", "gemm_tn.hip", "attention.hip", "attention_stream.hip", "attention_bwd.hip", "norm.hip",
            "elementwise.hip", "vae.hip", "vae_attention.hip", "train.hip", "fp32path.hip", "gradnorm.hip", "fifo.hip", "text.hip",
-           "gemm_nf4.hip"]
+           "gemm_nf4.hip", "lora.hip"]
 # translation units built without -amdgpu-mfma-vgpr-form (accumulators allowed into AGPRs): the 4-wave GEMM keeps the 256 accumulator
 # registers of a wave there, the one-wave-per-SIMD attention the output accumulators of up to five query tiles
 AGPR_SOURCES: set = {"gemm_bf16_4w.hip", "attention_stream.hip"}

@@ -513,7 +513,7 @@ class CTSDTrainer:
                  reference_latent_count=0, lr_scheduler=None, ddp_comm_dtype: Optional[torch.dtype] = None,
                  train_scheduler=None, optimizer_bits: int = 32, grad_conditioning: str = "torch",
                  activations: str = "recompute", activation_budget_gib: Optional[float] = None, deterministic: bool = False,
-                 graph: bool = False):
+                 graph: bool = False, lora=None):
         """common_config["frame_prediction_style"] (None | "diffusion_forcing" | "ctsd") and training_config select the
         training task mix of `make_input_for_prediction`; with "diffusion_forcing" every frame draws its own timestep
         (ctsd.py:1232-1237).  optimizer_bits: 32 = train.AdamW (fp32 moments), 8 = train.AdamW8bit (block-wise 8-bit moments: the
@@ -545,7 +545,15 @@ class CTSDTrainer:
         `graph_captures` / `graph_replays` count.  The graph is captured again when the keys, shapes or dtypes of the inputs change
         or the parameters' compute copies were replaced (a state-dict load, `.to()`); a forward of the model outside the trainer
         needs no recapture.  ValueError with ddp=True, with a clip or a scaler under grad_conditioning="torch", and for a model
-        that is not on the device.  False (default): every launch as before."""
+        that is not on the device.  False (default): every launch as before.
+        lora (MMDiT, one GPU, eager): None (default) = full fine-tuning, every launch as before.  A dict of
+        lora.LoraAdapters' keyword arguments (rank, alpha, target, generator) or a LoraAdapters built on this model = low-rank
+        fine-tuning: every base parameter is out of the optimizer, the targeted weights keep requires_grad (the block Functions
+        produce their dW), all others lose it (their weight-gradient GEMMs are skipped), the optimizer (`optimizer_bits`) holds the
+        adapter tensors only.  A step is backward, `project_grads_()`, the configured clip / scaler / grad_conditioning on the adapter
+        gradients, the optimizer step, `merge_()`; before every step the trainer re-merges if `lora.merged()` is False.
+        `save_checkpoint` / `load_checkpoint` write and read `<output>/lora/<step>.pth` in place of the base checkpoint.
+        ValueError with ddp=True and with graph=True, NotImplementedError with the SD 2.1 UNet."""
         from . import train as _train
         from .unet import UNetCrossviewTemporalConditionModel
         if activations not in _train.ACTIVATION_POLICIES:
@@ -553,6 +561,15 @@ class CTSDTrainer:
         if activation_budget_gib is not None and activation_budget_gib < 0:
             raise ValueError(f"activation_budget_gib: None or >= 0, got {activation_budget_gib!r}")
         self.is_unet = isinstance(model, UNetCrossviewTemporalConditionModel)
+        if lora is not None:
+            if ddp:
+                raise ValueError("CTSDTrainer(lora=...): ddp=True is not built (the adapter gradients are made after the backward, "
+                                 "outside the bucketed all-reduce); train one GPU per process")
+            if graph:
+                raise ValueError("CTSDTrainer(lora=...): graph=True is not built (the projection and the merge are not part of the "
+                                 "captured step); leave graph off")
+            if self.is_unet:
+                raise NotImplementedError("CTSDTrainer(lora=...) with the SD 2.1 UNet: only the MMDiT's linear layers are adapted")
         if self.is_unet and activations != "recompute":
             raise NotImplementedError(f"activations={activations!r} with the SD 2.1 UNet: its ResNet / transformer Functions "
                                       "(train_unet) have no kept-activation form yet, only the MMDiT blocks do")
@@ -596,9 +613,19 @@ class CTSDTrainer:
                 self.wrapper.register_comm_hook(None, default_hooks.bf16_compress_hook)
             elif ddp_comm_dtype not in (None, torch.float32):
                 raise ValueError("ddp_comm_dtype: torch.bfloat16, torch.float32 or None")
+        self.lora = None
+        if lora is not None:
+            from .lora import LoraAdapters
+            self.lora = lora if isinstance(lora, LoraAdapters) else LoraAdapters(model, **lora)
+            adapted = {id(p) for p in self.lora.targets()}
+            if not adapted <= {id(p) for p in model.parameters()}:
+                raise ValueError("CTSDTrainer(lora=...): the adapters were built on another model")
+            for p in model.parameters():            # targets: dW is wanted; everything else: frozen, its wgrad GEMMs are skipped
+                p.requires_grad_(id(p) in adapted)
         # every parameter, frozen ones included, as the reference builds it (ctsd.py:1089-1092): state-dict indices match
+        # (with adapters: the adapter tensors, and nothing of the base model)
         opt_cls = _train.AdamW8bit if optimizer_bits == 8 else _train.AdamW
-        self.optimizer = opt_cls(model.parameters(), lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self.optimizer = opt_cls(self._optimized(), lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         self.lr_scheduler = lr_scheduler(self.optimizer) if callable(lr_scheduler) else lr_scheduler
         self.global_step = 0
         self.sigmas = flow_match_train_sigmas(num_train_timesteps, shift)
@@ -629,6 +656,11 @@ class CTSDTrainer:
             from .schedulers import DDPMScheduler
             train_scheduler = DDPMScheduler(num_train_timesteps=num_train_timesteps)
         self.train_scheduler = train_scheduler
+
+    def _optimized(self) -> list:
+        """the parameters the optimizer steps and the clip reads: the model's, or with adapters theirs"""
+        lora = getattr(self, "lora", None)
+        return list(self.model.parameters() if lora is None else lora.parameters())
 
     @property
     def activation_plan(self):
@@ -745,6 +777,9 @@ class CTSDTrainer:
 
     def loss(self, latents: torch.Tensor, conditions: Dict[str, torch.Tensor], generator=None,
              timestep_indices=None, noise=None) -> torch.Tensor:
+        lora = getattr(self, "lora", None)
+        if lora is not None and not lora.merged():       # first forward, or the compute copies were dropped (state-dict load, .to(), bump):
+            lora.merge_()                                # never a silent forward of the base model
         return self._loss_of(self._stage_inputs(latents, conditions, generator, timestep_indices, noise))
 
     # ---- checkpoint / resume in the reference's on-disk layout (ctsd.py:1134-1155 save_checkpoint, :988-992 and
@@ -755,10 +790,16 @@ class CTSDTrainer:
         import torch.distributed as dist
         if dist.is_initialized() and dist.get_rank() != 0:
             return
-        os.makedirs(os.path.join(output_path, "checkpoints"), exist_ok=True)
         os.makedirs(os.path.join(output_path, "optimizer"), exist_ok=True)
-        torch.save({k: v.detach().cpu() for k, v in self.model.state_dict().items()},
-                   os.path.join(output_path, "checkpoints", f"{steps}.pth"))
+        lora = getattr(self, "lora", None)
+        if lora is not None:                        # the base model did not change: its checkpoint is not written again
+            os.makedirs(os.path.join(output_path, "lora"), exist_ok=True)
+            torch.save({"state": {k: v.detach().cpu() for k, v in lora.state_dict().items()}, "rank": lora.rank, "alpha": lora.alpha,
+                        "target": lora.target}, os.path.join(output_path, "lora", f"{steps}.pth"))
+        else:
+            os.makedirs(os.path.join(output_path, "checkpoints"), exist_ok=True)
+            torch.save({k: v.detach().cpu() for k, v in self.model.state_dict().items()},
+                       os.path.join(output_path, "checkpoints", f"{steps}.pth"))
         osd = self.optimizer.state_dict()
         osd["state"] = {i: {k: (v.detach().cpu() if torch.is_tensor(v) else v) for k, v in st.items()} for i, st in osd["state"].items()}
         torch.save(osd, os.path.join(output_path, "optimizer", f"{steps}.pth"))
@@ -769,8 +810,16 @@ class CTSDTrainer:
         (ctsd.py:1401-1404).  The lr_scheduler is NOT restored: the reference re-creates it on every start too."""
         import os
         self.global_step = int(resume_from)
-        self.model.load_state_dict(torch.load(os.path.join(output_path, "checkpoints", f"{resume_from}.pth"),
-                                              map_location="cpu", weights_only=True))
+        lora = getattr(self, "lora", None)
+        if lora is not None:                        # adapters + their optimizer state; the base model is the caller's
+            f = torch.load(os.path.join(output_path, "lora", f"{resume_from}.pth"), map_location="cpu", weights_only=True)
+            if int(f["rank"]) != lora.rank:
+                raise ValueError(f"load_checkpoint: the file holds rank {f['rank']}, the trainer's adapters rank {lora.rank}")
+            lora.alpha = float(f["alpha"])
+            lora.load_state_dict(f["state"])
+        else:
+            self.model.load_state_dict(torch.load(os.path.join(output_path, "checkpoints", f"{resume_from}.pth"),
+                                                  map_location="cpu", weights_only=True))
         self.optimizer.load_state_dict(torch.load(os.path.join(output_path, "optimizer", f"{resume_from}.pth"),
                                                   map_location="cpu", weights_only=True))
 
@@ -782,7 +831,7 @@ class CTSDTrainer:
         else:
             from .train import grad_norm_and_coef
             inv_scale = 1.0 if scaler is None else 1.0 / scaler.get_scale()
-            self.last_grad_norm, coef, found_inf = grad_norm_and_coef(self.model.parameters(), self.max_grad_norm, inv_scale)
+            self.last_grad_norm, coef, found_inf = grad_norm_and_coef(self._optimized(), self.max_grad_norm, inv_scale)
             if found_inf:
                 self.skipped_steps += 1
                 if scaler is None and not self._warned_nonfinite:
@@ -959,23 +1008,28 @@ class CTSDTrainer:
                 self.lr_scheduler.step()
             self.global_step = gs + 1
             return loss
+        lora = getattr(self, "lora", None)
         sync = contextlib.nullcontext() if (should_optimize or not self.ddp) else self.wrapper.no_sync()
         with sync:
             loss = self.loss(latents, conditions, generator, timestep_indices, noise)
             (loss if scaler is None else scaler.scale(loss)).backward()                   # :1401-1404
+        if lora is not None:                             # dW of the targets -> A.grad, B.grad (accumulated); dW is dropped
+            lora.project_grads_()
         if should_optimize and getattr(self, "grad_conditioning", "torch") == "fused":
             self._fused_optimizer_step(scaler)
         elif should_optimize:
             if self.max_grad_norm is not None:
                 if scaler is not None:
                     scaler.unscale_(self.optimizer)                                      # :1411-1413
-                torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.max_grad_norm)
+                torch.nn.utils.clip_grad_norm_(self._optimized(), self.max_grad_norm)
             if scaler is not None:
                 scaler.step(self.optimizer)                                              # :1426-1428 (skips on inf / nan)
                 scaler.update()
             else:
                 self.optimizer.step()
             self.optimizer.zero_grad()
+        if should_optimize and lora is not None:         # the new A, B reach the next forward through the compute copies
+            lora.merge_()
         if getattr(self, "graph", False):            # an eager warm-up step of graph mode
             self._g_eager_done += 1
             self._g_grads_fresh = should_optimize

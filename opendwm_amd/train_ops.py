@@ -459,6 +459,94 @@ def grad_scale_multi_(gs, coef: float) -> None:
     _call("dwm_grad_scale_multi", _p(items), _p(tab.block_item), _p(tab.block_start), tab.block_item.numel(), GRAD_CHUNK, coef)
 
 
+# ---- low-rank adapters (lora.hip; include/dwm_hip.h "Low-rank adapters"): W + scale * B A over a list of weights
+LORA_TILE_ROWS, LORA_TILE_COLS, LORA_DA_ROWS = 32, 128, 512      # the tile of the kernels and the rows behind one dA partial
+LORA_FIN_CHUNK = 1 << 14                                         # elements of dA per workgroup of the finishing launch
+
+
+class LoraTables:
+    """the block tables of a list of (N, K, r) shapes on its device: .merge (32 x 128 tiles), .da (512-row chunk x 128 columns),
+    .fin (runs of LORA_FIN_CHUNK of r * K) and .db (32 rows).  They depend on the shapes only: a caller with a fixed list keeps them."""
+    def __init__(self, dev: torch.device, shapes):
+        cd = lambda a, b: (a + b - 1) // b
+        self.shapes, self.device = tuple(tuple(s) for s in shapes), dev
+        self.merge = _BlockTables(dev, 1, tuple(cd(N, LORA_TILE_ROWS) * cd(K, LORA_TILE_COLS) for N, K, r in self.shapes))
+        self.da = _BlockTables(dev, 1, tuple(cd(N, LORA_DA_ROWS) * cd(K, LORA_TILE_COLS) for N, K, r in self.shapes))
+        self.fin = _BlockTables(dev, LORA_FIN_CHUNK, tuple(r * K for N, K, r in self.shapes))
+        self.db = _BlockTables(dev, 1, tuple(cd(N, LORA_TILE_ROWS) for N, K, r in self.shapes))
+
+
+def _lora_items(ws, as_, bs, outs, out2s, scratch, scales, what: str, out_dtypes: tuple):
+    """(host item array, its device copy, shapes) of dwm_lora_item rows.  The dtypes, devices, contiguity and the agreement of the
+    shapes are checked here; the limits on r and K are the library's (DWM_EUNSUPPORTED)."""
+    import struct
+    dev = ws[0].device
+    rows, shapes = [], []
+    for i, (w, a, b, out, scale) in enumerate(zip(ws, as_, bs, outs, scales)):
+        for t, dts, name in ((w, (torch.float32, bf16), "the weight / gradient"), (a, (torch.float32,), "A"), (b, (torch.float32,), "B"),
+                             (out, out_dtypes, "the output")):
+            if not t.is_cuda or t.device != dev or t.dtype not in dts or not t.is_contiguous():
+                raise RuntimeError(f"{what}: {name} of entry {i} must be a contiguous {' / '.join(str(d) for d in dts)} tensor on "
+                                   "one HIP device (there is no CPU fallback)")
+        if w.dim() != 2 or a.dim() != 2 or b.dim() != 2 or a.shape[1] != w.shape[1] or b.shape != (w.shape[0], a.shape[0]):
+            raise RuntimeError(f"{what}: entry {i}: W [N, K], A [r, K] and B [N, r] expected, got {tuple(w.shape)}, {tuple(a.shape)}, "
+                               f"{tuple(b.shape)}")
+        N, K = w.shape
+        r = a.shape[0]
+        if out2s is None:
+            if out.shape != w.shape:
+                raise RuntimeError(f"{what}: entry {i}: out must have W's shape")
+            out2, sc = 0, 0
+        else:
+            d2 = out2s[i]
+            if out.shape != a.shape or d2.shape != b.shape or d2.dtype != torch.float32 or not d2.is_contiguous() or d2.device != dev:
+                raise RuntimeError(f"{what}: entry {i}: dA and dB must be contiguous fp32 tensors of A's and B's shapes")
+            out2, sc = d2.data_ptr(), scratch[i].data_ptr()
+        flags = int(w.dtype == bf16) | (int(out.dtype == bf16) << 1)
+        rows.append((w.data_ptr(), a.data_ptr(), b.data_ptr(), out.data_ptr(), out2, sc, N, K, r | (flags << 32),
+                     struct.unpack("<I", struct.pack("<f", float(scale)))[0], r * K))
+        shapes.append((N, K, r))
+    host = torch.tensor(rows, dtype=torch.int64)                  # [n, 11] = dwm_lora_item[n]
+    return host, host.to(dev, non_blocking=True), tuple(shapes)
+
+
+def lora_merge_multi(ws, as_, bs, outs, scales, tables: Optional[LoraTables] = None) -> None:
+    """dwm_lora_merge_multi: outs[i] = ws[i] + scales[i] * bs[i] @ as_[i] for the whole list in one launch.  ws / outs fp32 or bf16
+    [N, K] (out may be w itself: the in-place fold), as_ fp32 [r, K], bs fp32 [N, r].  bf16 out = the merge (a compute copy),
+    fp32 out = the fold; the arithmetic is stated at the prototype."""
+    if not ws:
+        return
+    host, items, shapes = _lora_items(ws, as_, bs, outs, None, None, scales, "lora_merge_multi", (torch.float32, bf16))
+    tab = tables if tables is not None and tables.shapes == shapes and tables.device == items.device else LoraTables(items.device, shapes)
+    _call("dwm_lora_merge_multi", host.data_ptr(), len(shapes), _p(items), _p(tab.merge.block_item), _p(tab.merge.block_start),
+          tab.merge.block_item.numel())
+
+
+def lora_project_multi(gs, as_, bs, das, dbs, scales, accumulate: bool = False, tables: Optional[LoraTables] = None,
+                       return_partials: bool = False):
+    """dwm_lora_project_multi: das[i] (+)= scales[i] * bs[i]^T @ gs[i], dbs[i] (+)= scales[i] * gs[i] @ as_[i]^T for the whole list
+    (three launches).  gs fp32 or bf16 [N, K]; das / dbs fp32, overwritten unless `accumulate`.  No atomics: equal bits every time.
+    return_partials (tests): the dA partials of every entry, [row chunks, r, K]."""
+    if not gs:
+        return [] if return_partials else None
+    dev = gs[0].device
+    query = _lib.load().dwm_lora_project_ws_floats
+    sizes = [max(int(query(g.shape[0], g.shape[1], a.shape[0])), 4) if g.dim() == 2 and a.dim() == 2 else 4 for g, a in zip(gs, as_)]
+    offs = [0]
+    for s in sizes:
+        offs.append(offs[-1] + (s + 3) // 4 * 4)
+    scratch = torch.empty(offs[-1], dtype=torch.float32, device=dev)
+    parts = [scratch[o:o + s] for o, s in zip(offs, sizes)]
+    host, items, shapes = _lora_items(gs, as_, bs, das, dbs, parts, scales, "lora_project_multi", (torch.float32,))
+    tab = tables if tables is not None and tables.shapes == shapes and tables.device == items.device else LoraTables(items.device, shapes)
+    _call("dwm_lora_project_multi", host.data_ptr(), len(shapes), _p(items), _p(tab.da.block_item), _p(tab.da.block_start),
+          tab.da.block_item.numel(), _p(tab.fin.block_item), _p(tab.fin.block_start), tab.fin.block_item.numel(), LORA_FIN_CHUNK,
+          _p(tab.db.block_item), _p(tab.db.block_start), tab.db.block_item.numel(), int(accumulate))
+    if return_partials:
+        return [p.view(-1, r, K) for p, (N, K, r) in zip(parts, shapes)]
+    return None
+
+
 # ------------------------------------------------------------------------------------------ composites
 def linear_dgrad(dy: torch.Tensor, w_t: torch.Tensor, out: Optional[torch.Tensor] = None, **epi) -> torch.Tensor:
     """dX [M, K] = dY [M, N] @ W [N, K], with W^T [K, N] given (the GEMM contracts over the columns of
