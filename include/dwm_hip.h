@@ -633,6 +633,54 @@ int dwm_adamw8_multi_dev(const dwm_adamw8_item* items, const int32_t* block_item
                          int64_t chunk, const float* code_m, const float* code_v, const float* hyper, const float* cond,
                          float beta1, float beta2, float eps, float weight_decay, void* stream);
 
+/* EMA weights: an exponential moving average of the fp32 master parameters kept in one fp32 shadow per tensor (the semantics of
+ * diffusers' EMAModel; DESIGN s27).  Element rule of every entry point below, in fp32:
+ *     e' = e + omd * (p' - e),       omd = 1 - decay, one scalar per launch, p' = the value the same thread stores to p.
+ * Two uniform special cases: omd == 0 leaves e bit-unchanged (the shadows are neither read nor written), omd == 1 stores p' exactly.
+ *
+ * dwm_adamw_ema_multi / dwm_adamw8_ema_multi: dwm_adamw_multi / dwm_adamw8_multi with the average updated in the same pass - 38
+ * instead of 30 bytes per parameter (26 instead of 18), where a separate pass moves 12.  The items are the existing ones with one
+ * more pointer, `ema`, before n; ema == NULL: that tensor has no shadow and is updated exactly as by the plain entry (mixed lists).
+ * p, m, v, the absmax scales and the bf16 copy are bit-equal to what the plain entry points write on the same inputs (one kernel
+ * body).  one_minus_decay outside [0, 1] or NaN: DWM_EINVAL; the other status codes are those of the plain entries.
+ * The _dev forms read omd from hyper[3] (hyper: at least 4 floats); cond[2] != 0 changes nothing, shadows included.
+ * All pointers need 4-byte alignment only (the 8-bit form takes its vector path where p, g and the shadow are 16-byte aligned, the
+ * codes 4-byte, the bf16 copy 8-byte); no byte outside [ptr, ptr + n) is touched. */
+typedef struct dwm_adamw_ema_item {
+    float* p; const float* g; float* m; float* v; void* p_bf16; float* ema; int64_t n;
+} dwm_adamw_ema_item;
+typedef struct dwm_adamw8_ema_item {
+    float* p; const float* g; uint8_t* m_q; float* m_absmax; uint8_t* v_q; float* v_absmax; void* p_bf16; float* ema; int64_t n;
+} dwm_adamw8_ema_item;
+int dwm_adamw_ema_multi(const dwm_adamw_ema_item* items, const int32_t* block_item, const int64_t* block_start, int64_t n_blocks,
+                        int64_t chunk, float lr, float beta1, float beta2, float eps, float weight_decay, float bias_corr1,
+                        float bias_corr2, float grad_scale, float one_minus_decay, void* stream);
+int dwm_adamw8_ema_multi(const dwm_adamw8_ema_item* items, const int32_t* block_item, const int64_t* block_start, int64_t n_blocks,
+                         int64_t chunk, const float* code_m, const float* code_v, float lr, float beta1, float beta2, float eps,
+                         float weight_decay, float bias_corr1, float bias_corr2, float grad_scale, float one_minus_decay,
+                         void* stream);
+int dwm_adamw_ema_multi_dev(const dwm_adamw_ema_item* items, const int32_t* block_item, const int64_t* block_start, int64_t n_blocks,
+                            int64_t chunk, const float* hyper, const float* cond, float beta1, float beta2, float eps,
+                            float weight_decay, void* stream);
+int dwm_adamw8_ema_multi_dev(const dwm_adamw8_ema_item* items, const int32_t* block_item, const int64_t* block_start,
+                             int64_t n_blocks, int64_t chunk, const float* code_m, const float* code_v, const float* hyper,
+                             const float* cond, float beta1, float beta2, float eps, float weight_decay, void* stream);
+
+/* The element rule without an optimizer step (p is read only): for parameters that have a shadow but no gradient in a step, and
+ * for callers with an optimizer of their own.  hyper non-NULL (device, at least 4 floats): omd = hyper[3] and one_minus_decay is
+ * ignored; hyper NULL: one_minus_decay outside [0, 1] or NaN is DWM_EINVAL.  cond non-NULL (device, at least 3 floats) with
+ * cond[2] != 0: nothing is changed.  hyper or cond not 4-byte aligned: DWM_EALIGN. */
+typedef struct dwm_ema_item { float* ema; const float* p; int64_t n; } dwm_ema_item;
+int dwm_ema_multi(const dwm_ema_item* items, const int32_t* block_item, const int64_t* block_start, int64_t n_blocks,
+                  int64_t chunk, float one_minus_decay, const float* hyper, const float* cond, void* stream);
+
+/* p <-> ema element by element, in place and without scratch memory (evaluation with the averaged weights: no third copy of
+ * the parameters); p_bf16 (optional) receives the bf16 of the NEW p, rounded as by the AdamW kernels and dwm_cast_f32_to_bf16.
+ * Two calls restore every byte. */
+typedef struct dwm_ema_swap_item { float* p; float* ema; void* p_bf16; int64_t n; } dwm_ema_swap_item;
+int dwm_ema_swap_multi(const dwm_ema_swap_item* items, const int32_t* block_item, const int64_t* block_start, int64_t n_blocks,
+                       int64_t chunk, void* stream);
+
 /* Gradient norm, clip coefficient and non-finite check of a LIST of fp32 gradients in one read (the work of
  * torch.amp.GradScaler.unscale_ + torch.nn.utils.clip_grad_norm_ + the found-inf check of GradScaler.step, ctsd.py:1401-1432).
  * items / block_item / block_start are DEVICE arrays with the meaning they have for dwm_adamw_multi; chunk: a multiple of 1024,

@@ -116,7 +116,25 @@ class AdamW8Item(C.Structure):          # one row of the device array train_ops.
     _fields_ = [("p", _vp), ("g", _vp), ("m_q", _vp), ("m_absmax", _vp), ("v_q", _vp), ("v_absmax", _vp), ("p_bf16", _vp), ("n", _i64)]
 
 
-class FifoItem(C.Structure):            # one entry of the list dwm_fifo_slide_multi slides (8 x 8 bytes; host array and device copy)
+# rows of the device arrays of the EMA entry points (train_ops.adamw_ema_multi_, adamw8_ema_multi_, ema_multi_, ema_swap_multi_)
+class AdamWEmaItem(C.Structure):        # dwm_adamw_ema_item (7 x 8 bytes)
+    _fields_ = [("p", _vp), ("g", _vp), ("m", _vp), ("v", _vp), ("p_bf16", _vp), ("ema", _vp), ("n", _i64)]
+
+
+class AdamW8EmaItem(C.Structure):       # dwm_adamw8_ema_item (9 x 8 bytes)
+    _fields_ = [("p", _vp), ("g", _vp), ("m_q", _vp), ("m_absmax", _vp), ("v_q", _vp), ("v_absmax", _vp), ("p_bf16", _vp),
+                ("ema", _vp), ("n", _i64)]
+
+
+class EmaItem(C.Structure):             # dwm_ema_item (3 x 8 bytes)
+    _fields_ = [("ema", _vp), ("p", _vp), ("n", _i64)]
+
+
+class EmaSwapItem(C.Structure):         # dwm_ema_swap_item (4 x 8 bytes)
+    _fields_ = [("p", _vp), ("ema", _vp), ("p_bf16", _vp), ("n", _i64)]
+
+
+class FifoItem(C.Structure):           # one entry of the list dwm_fifo_slide_multi slides (8 x 8 bytes; host array and device copy)
     _fields_ = [("buf", _vp), ("fresh", _vp), ("outer", _i64), ("T", _i64), ("inner_bytes", _i64), ("fresh_outer", _i64),
                 ("convert", _i64), ("n", _i64)]
 
@@ -226,6 +244,13 @@ SIGNATURES = {
     "dwm_adamw8_multi": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp]),
     "dwm_adamw_multi_dev": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _vp]),
     "dwm_adamw8_multi_dev": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _vp]),
+    # EMA weights: the plain entries' arguments + one_minus_decay before the stream (by value) / hyper[3] (_dev); update; exchange
+    "dwm_adamw_ema_multi": (_i32, [_vp, _vp, _vp, _i64, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp]),
+    "dwm_adamw8_ema_multi": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp]),
+    "dwm_adamw_ema_multi_dev": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _vp]),
+    "dwm_adamw8_ema_multi_dev": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _vp]),
+    "dwm_ema_multi": (_i32, [_vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp]),
+    "dwm_ema_swap_multi": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp]),
     "dwm_grad_sumsq_multi": (_i32, [_vp, _vp, _vp, _i64, _i64, _f32, _f32, _vp, _vp, _vp, _vp]),
     "dwm_grad_scale_multi": (_i32, [_vp, _vp, _vp, _i64, _i64, _f32, _vp]),
     "dwm_block_permute": (_i32, [C.POINTER(BlockPermuteArgs), _vp]),

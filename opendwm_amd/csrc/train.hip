@@ -610,21 +610,39 @@ adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restri
 
 // The same update for MANY tensors in one launch: block b works on elements [block_start[b], block_start[b] + chunk) of tensor
 // block_item[b] (a model has 1.4-1.7 k parameter tensors: per-tensor launches made the optimizer step launch-bound).
-DWM_DEVINL void adamw_multi_body(const dwm_adamw_item* __restrict__ items, const int32_t* __restrict__ block_item,
-                                 const int64_t* __restrict__ block_start, int64_t chunk, const AdamwHyper& h) {
+//
+// Exponential moving average of the weights (dwm_adamw_ema_multi & co., DESIGN s27): e' = e + omd * (p' - e) in fp32, p' the value
+// the same thread stores to p, omd = 1 - decay uniform over the launch.  The two ends of the range are exact: omd == 0 touches no
+// shadow at all, omd == 1 stores p' itself.
+DWM_DEVINL float ema_update(float e, float p_new, float omd) { return omd == 1.f ? p_new : e + omd * (p_new - e); }
+
+// the shadow pointer of a list item: null for the item types that have none
+DWM_DEVINL float* item_ema(const dwm_adamw_item&) { return nullptr; }
+DWM_DEVINL float* item_ema(const dwm_adamw8_item&) { return nullptr; }
+DWM_DEVINL float* item_ema(const dwm_adamw_ema_item& it) { return it.ema; }
+DWM_DEVINL float* item_ema(const dwm_adamw8_ema_item& it) { return it.ema; }
+
+// Item = dwm_adamw_item (omd is not read) or dwm_adamw_ema_item: the shadow, where the item has one and omd != 0, is read after g, p,
+// m, v and written after them - the parameter update is the same sequence in both instantiations.
+template <typename Item>
+DWM_DEVINL void adamw_multi_body(const Item* __restrict__ items, const int32_t* __restrict__ block_item,
+                                 const int64_t* __restrict__ block_start, int64_t chunk, const AdamwHyper& h, float omd) {
     int64_t i0, i1;
-    const dwm_adamw_item it = dwm_list_chunk(items, block_item, block_start, chunk, i0, i1);
+    const Item it = dwm_list_chunk(items, block_item, block_start, chunk, i0, i1);
     float* __restrict__ p = it.p;
     const float* __restrict__ g = it.g;
     float* __restrict__ m = it.m;
     float* __restrict__ v = it.v;
     bf16_t* __restrict__ pb = (bf16_t*)it.p_bf16;
+    float* __restrict__ ema = omd != 0.f ? item_ema(it) : nullptr;
     for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
         const float gi = g[i], p0 = p[i];
         float mi = m[i], vi = v[i];
+        const float e0 = ema ? ema[i] : 0.f;
         const float pi = adamw_update(p0, gi, mi, vi, h);
         p[i] = pi; m[i] = mi; v[i] = vi;
         if (pb) pb[i] = f32_to_bf16(pi);
+        if (ema) ema[i] = ema_update(e0, pi, omd);
     }
 }
 
@@ -632,7 +650,14 @@ __global__ void __launch_bounds__(256)
 adamw_multi_kernel(const dwm_adamw_item* __restrict__ items, const int32_t* __restrict__ block_item,
                    const int64_t* __restrict__ block_start, int64_t chunk, float lr, float b1, float b2, float eps, float wd,
                    float bc1, float bc2, float gscale) {
-    adamw_multi_body(items, block_item, block_start, chunk, AdamwHyper{lr, b1, b2, eps, wd, bc1, bc2, gscale});
+    adamw_multi_body(items, block_item, block_start, chunk, AdamwHyper{lr, b1, b2, eps, wd, bc1, bc2, gscale}, 0.f);
+}
+
+__global__ void __launch_bounds__(256)
+adamw_ema_multi_kernel(const dwm_adamw_ema_item* __restrict__ items, const int32_t* __restrict__ block_item,
+                       const int64_t* __restrict__ block_start, int64_t chunk, float lr, float b1, float b2, float eps, float wd,
+                       float bc1, float bc2, float gscale, float omd) {
+    adamw_multi_body(items, block_item, block_start, chunk, AdamwHyper{lr, b1, b2, eps, wd, bc1, bc2, gscale}, omd);
 }
 
 // The per-step scalars from DEVICE memory (dwm_adamw_multi_dev / dwm_adamw8_multi_dev): hyper = [lr, bias_corr1, bias_corr2, _],
@@ -652,7 +677,50 @@ adamw_multi_dev_kernel(const dwm_adamw_item* __restrict__ items, const int32_t* 
                        const float* __restrict__ cond, float b1, float b2, float eps, float wd) {
     AdamwHyper h;
     if (!adamw_dev_hyper(hyper, cond, b1, b2, eps, wd, h)) return;
-    adamw_multi_body(items, block_item, block_start, chunk, h);
+    adamw_multi_body(items, block_item, block_start, chunk, h, 0.f);
+}
+
+// hyper[3] = omd (the slot dwm_adamw_multi_dev leaves unused)
+__global__ void __launch_bounds__(256)
+adamw_ema_multi_dev_kernel(const dwm_adamw_ema_item* __restrict__ items, const int32_t* __restrict__ block_item,
+                           const int64_t* __restrict__ block_start, int64_t chunk, const float* __restrict__ hyper,
+                           const float* __restrict__ cond, float b1, float b2, float eps, float wd) {
+    AdamwHyper h;
+    if (!adamw_dev_hyper(hyper, cond, b1, b2, eps, wd, h)) return;
+    adamw_multi_body(items, block_item, block_start, chunk, h, hyper[3]);
+}
+
+// The average alone (dwm_ema_multi): parameters that have a shadow but no gradient in a step, and callers with an optimizer of their
+// own.  hyper / cond as above, both optional.
+__global__ void __launch_bounds__(256)
+ema_multi_kernel(const dwm_ema_item* __restrict__ items, const int32_t* __restrict__ block_item,
+                 const int64_t* __restrict__ block_start, int64_t chunk, float omd_value, const float* __restrict__ hyper,
+                 const float* __restrict__ cond) {
+    if (cond && cond[2] != 0.f) return;
+    const float omd = hyper ? hyper[3] : omd_value;
+    if (omd == 0.f) return;
+    int64_t i0, i1;
+    const dwm_ema_item it = dwm_list_chunk(items, block_item, block_start, chunk, i0, i1);
+    float* __restrict__ ema = it.ema;
+    const float* __restrict__ p = it.p;
+    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) ema[i] = ema_update(ema[i], p[i], omd);
+}
+
+// p <-> ema element by element, the bf16 copy of the new p beside it (dwm_ema_swap_multi): a thread holds both values of its
+// element before it stores either, so there is nothing to stage
+__global__ void __launch_bounds__(256)
+ema_swap_multi_kernel(const dwm_ema_swap_item* __restrict__ items, const int32_t* __restrict__ block_item,
+                      const int64_t* __restrict__ block_start, int64_t chunk) {
+    int64_t i0, i1;
+    const dwm_ema_swap_item it = dwm_list_chunk(items, block_item, block_start, chunk, i0, i1);
+    float* __restrict__ p = it.p;
+    float* __restrict__ ema = it.ema;
+    bf16_t* __restrict__ pb = (bf16_t*)it.p_bf16;
+    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
+        const float a = p[i], b = ema[i];
+        p[i] = b; ema[i] = a;
+        if (pb) pb[i] = f32_to_bf16(b);
+    }
 }
 
 // ---------------------------------------------------------------------------------- block-wise 8-bit optimizer state
@@ -781,15 +849,20 @@ dequantize_blockwise8_kernel(const uint8_t* __restrict__ q, const float* __restr
 // adamw_multi_kernel with both moments in the 8-bit format: decode, the same update, re-encode, in one pass (18 bytes per
 // parameter instead of 30).  The parameter update uses the fresh fp32 moments; quantisation only affects what the next step
 // starts from.  Wave w of a workgroup takes blocks w, w + 4, ... of the workgroup's chunk (a multiple of 256 elements).
-DWM_DEVINL void adamw8_multi_body(const dwm_adamw8_item* __restrict__ items, const int32_t* __restrict__ block_item,
+// Item = dwm_adamw8_item or dwm_adamw8_ema_item (the shadow, where the item has one and omd != 0, is moved behind the update of its
+// block; it takes the vector access where the rest of the block does and the shadow itself is 16-byte aligned).
+template <typename Item>
+DWM_DEVINL void adamw8_multi_body(const Item* __restrict__ items, const int32_t* __restrict__ block_item,
                                   const int64_t* __restrict__ block_start, int64_t chunk, const float* __restrict__ code_m,
-                                  const float* __restrict__ code_v, const AdamwHyper& h) {
+                                  const float* __restrict__ code_v, const AdamwHyper& h, float omd) {
     __shared__ float tab_m[512], tab_v[512];
     q8_stage_table(code_m, tab_m);
     q8_stage_table(code_v, tab_v);
     __syncthreads();
     int64_t i0, i1;
-    const dwm_adamw8_item it = dwm_list_chunk(items, block_item, block_start, chunk, i0, i1);
+    const Item it = dwm_list_chunk(items, block_item, block_start, chunk, i0, i1);
+    float* __restrict__ ema = omd != 0.f ? item_ema(it) : nullptr;
+    const bool vec_e = q8_aligned(ema, 16);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* __restrict__ p = it.p;
     const float* __restrict__ g = it.g;
@@ -829,6 +902,18 @@ DWM_DEVINL void adamw8_multi_body(const dwm_adamw8_item* __restrict__ items, con
         q8_store4c(mq, e, it.n, full, q8_encode4(tab_m, mi, am, zm, false));
         q8_store4c(vq, e, it.n, full, q8_encode4(tab_v, vi, av, zv, true));
         if (lane == 0) { it.m_absmax[blk] = am; it.v_absmax[blk] = av; }
+        if (ema) {
+            // The average is a pass of its own behind the update of the block: it reads back the p' this lane has just stored (a
+            // cache hit) rather than using the registers.  Any further use of the update's values changes how the compiler packs
+            // and contracts the update itself (seen: the last bit of m), and p, m, v must be the plain kernel's bits.
+            __asm__ volatile("" ::: "memory");
+            float pn[4], ei[4];
+            q8_load4f(p, e, it.n, full, pn);
+            q8_load4f(ema, e, it.n, full && vec_e, ei);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) ei[j] = ema_update(ei[j], pn[j], omd);
+            q8_store4f(ema, e, it.n, full && vec_e, ei);
+        }
     }
 }
 
@@ -837,7 +922,15 @@ adamw8_multi_kernel(const dwm_adamw8_item* __restrict__ items, const int32_t* __
                     const int64_t* __restrict__ block_start, int64_t chunk, const float* __restrict__ code_m,
                     const float* __restrict__ code_v, float lr, float b1, float b2, float eps, float wd,
                     float bc1, float bc2, float gscale) {
-    adamw8_multi_body(items, block_item, block_start, chunk, code_m, code_v, AdamwHyper{lr, b1, b2, eps, wd, bc1, bc2, gscale});
+    adamw8_multi_body(items, block_item, block_start, chunk, code_m, code_v, AdamwHyper{lr, b1, b2, eps, wd, bc1, bc2, gscale}, 0.f);
+}
+
+__global__ void __launch_bounds__(256)
+adamw8_ema_multi_kernel(const dwm_adamw8_ema_item* __restrict__ items, const int32_t* __restrict__ block_item,
+                        const int64_t* __restrict__ block_start, int64_t chunk, const float* __restrict__ code_m,
+                        const float* __restrict__ code_v, float lr, float b1, float b2, float eps, float wd,
+                        float bc1, float bc2, float gscale, float omd) {
+    adamw8_multi_body(items, block_item, block_start, chunk, code_m, code_v, AdamwHyper{lr, b1, b2, eps, wd, bc1, bc2, gscale}, omd);
 }
 
 // (the flag is uniform over the launch: every thread of a skipped launch leaves before the first barrier of the body)
@@ -848,7 +941,17 @@ adamw8_multi_dev_kernel(const dwm_adamw8_item* __restrict__ items, const int32_t
                         float b1, float b2, float eps, float wd) {
     AdamwHyper h;
     if (!adamw_dev_hyper(hyper, cond, b1, b2, eps, wd, h)) return;
-    adamw8_multi_body(items, block_item, block_start, chunk, code_m, code_v, h);
+    adamw8_multi_body(items, block_item, block_start, chunk, code_m, code_v, h, 0.f);
+}
+
+__global__ void __launch_bounds__(256)
+adamw8_ema_multi_dev_kernel(const dwm_adamw8_ema_item* __restrict__ items, const int32_t* __restrict__ block_item,
+                            const int64_t* __restrict__ block_start, int64_t chunk, const float* __restrict__ code_m,
+                            const float* __restrict__ code_v, const float* __restrict__ hyper, const float* __restrict__ cond,
+                            float b1, float b2, float eps, float wd) {
+    AdamwHyper h;
+    if (!adamw_dev_hyper(hyper, cond, b1, b2, eps, wd, h)) return;
+    adamw8_multi_body(items, block_item, block_start, chunk, code_m, code_v, h, hyper[3]);
 }
 
 __global__ void __launch_bounds__(256)
@@ -1240,6 +1343,70 @@ extern "C" int dwm_adamw8_multi_dev(const dwm_adamw8_item* items, const int32_t*
     if (const int rc = adamw_dev_operands(hyper, cond)) return rc;
     hipLaunchKernelGGL(adamw8_multi_dev_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, items, block_item,
                        block_start, chunk, code_m, code_v, hyper, cond, beta1, beta2, eps, weight_decay);
+    return dwm_launch_status();
+}
+
+// ---- EMA of the weights: the four fused entries, the stand-alone update and the exchange (include/dwm_hip.h, "EMA weights")
+static bool ema_bad_omd(float one_minus_decay) { return !(one_minus_decay >= 0.f && one_minus_decay <= 1.f); }      // NaN included
+
+extern "C" int dwm_adamw_ema_multi(const dwm_adamw_ema_item* items, const int32_t* block_item, const int64_t* block_start,
+                                   int64_t n_blocks, int64_t chunk, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                   float bias_corr1, float bias_corr2, float grad_scale, float one_minus_decay, void* stream) {
+    if (dwm_bad_list_tables(items, block_item, block_start, n_blocks, chunk) || bias_corr1 <= 0.f || bias_corr2 <= 0.f ||
+        ema_bad_omd(one_minus_decay)) return DWM_EINVAL;
+    hipLaunchKernelGGL(adamw_ema_multi_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, items, block_item,
+                       block_start, chunk, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale, one_minus_decay);
+    return dwm_launch_status();
+}
+
+extern "C" int dwm_adamw_ema_multi_dev(const dwm_adamw_ema_item* items, const int32_t* block_item, const int64_t* block_start,
+                                       int64_t n_blocks, int64_t chunk, const float* hyper, const float* cond, float beta1,
+                                       float beta2, float eps, float weight_decay, void* stream) {
+    if (dwm_bad_list_tables(items, block_item, block_start, n_blocks, chunk)) return DWM_EINVAL;
+    if (const int rc = adamw_dev_operands(hyper, cond)) return rc;
+    hipLaunchKernelGGL(adamw_ema_multi_dev_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, items, block_item,
+                       block_start, chunk, hyper, cond, beta1, beta2, eps, weight_decay);
+    return dwm_launch_status();
+}
+
+extern "C" int dwm_adamw8_ema_multi(const dwm_adamw8_ema_item* items, const int32_t* block_item, const int64_t* block_start,
+                                    int64_t n_blocks, int64_t chunk, const float* code_m, const float* code_v, float lr, float beta1,
+                                    float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2, float grad_scale,
+                                    float one_minus_decay, void* stream) {
+    if (dwm_bad_list_tables(items, block_item, block_start, n_blocks, chunk) || !code_m || !code_v || chunk % Q8_BLOCK != 0 ||
+        bias_corr1 <= 0.f || bias_corr2 <= 0.f || ema_bad_omd(one_minus_decay)) return DWM_EINVAL;
+    hipLaunchKernelGGL(adamw8_ema_multi_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, items, block_item,
+                       block_start, chunk, code_m, code_v, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale,
+                       one_minus_decay);
+    return dwm_launch_status();
+}
+
+extern "C" int dwm_adamw8_ema_multi_dev(const dwm_adamw8_ema_item* items, const int32_t* block_item, const int64_t* block_start,
+                                        int64_t n_blocks, int64_t chunk, const float* code_m, const float* code_v, const float* hyper,
+                                        const float* cond, float beta1, float beta2, float eps, float weight_decay, void* stream) {
+    if (dwm_bad_list_tables(items, block_item, block_start, n_blocks, chunk) || !code_m || !code_v || chunk % Q8_BLOCK != 0)
+        return DWM_EINVAL;
+    if (const int rc = adamw_dev_operands(hyper, cond)) return rc;
+    hipLaunchKernelGGL(adamw8_ema_multi_dev_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, items, block_item,
+                       block_start, chunk, code_m, code_v, hyper, cond, beta1, beta2, eps, weight_decay);
+    return dwm_launch_status();
+}
+
+extern "C" int dwm_ema_multi(const dwm_ema_item* items, const int32_t* block_item, const int64_t* block_start, int64_t n_blocks,
+                             int64_t chunk, float one_minus_decay, const float* hyper, const float* cond, void* stream) {
+    if (dwm_bad_list_tables(items, block_item, block_start, n_blocks, chunk) || (!hyper && ema_bad_omd(one_minus_decay)))
+        return DWM_EINVAL;
+    if ((((uintptr_t)hyper) & 3u) != 0 || (((uintptr_t)cond) & 3u) != 0) return DWM_EALIGN;
+    hipLaunchKernelGGL(ema_multi_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, items, block_item, block_start,
+                       chunk, one_minus_decay, hyper, cond);
+    return dwm_launch_status();
+}
+
+extern "C" int dwm_ema_swap_multi(const dwm_ema_swap_item* items, const int32_t* block_item, const int64_t* block_start,
+                                  int64_t n_blocks, int64_t chunk, void* stream) {
+    if (dwm_bad_list_tables(items, block_item, block_start, n_blocks, chunk)) return DWM_EINVAL;
+    hipLaunchKernelGGL(ema_swap_multi_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, items, block_item,
+                       block_start, chunk);
     return dwm_launch_status();
 }
 

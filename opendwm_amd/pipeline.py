@@ -7,6 +7,7 @@ unchanged ctsd.py drives the same model class.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, Optional
 
 import torch
@@ -513,7 +514,7 @@ class CTSDTrainer:
                  reference_latent_count=0, lr_scheduler=None, ddp_comm_dtype: Optional[torch.dtype] = None,
                  train_scheduler=None, optimizer_bits: int = 32, grad_conditioning: str = "torch",
                  activations: str = "recompute", activation_budget_gib: Optional[float] = None, deterministic: bool = False,
-                 graph: bool = False, lora=None):
+                 graph: bool = False, lora=None, ema=None):
         """common_config["frame_prediction_style"] (None | "diffusion_forcing" | "ctsd") and training_config select the
         training task mix of `make_input_for_prediction`; with "diffusion_forcing" every frame draws its own timestep
         (ctsd.py:1232-1237).  optimizer_bits: 32 = train.AdamW (fp32 moments), 8 = train.AdamW8bit (block-wise 8-bit moments: the
@@ -553,7 +554,16 @@ class CTSDTrainer:
         adapter tensors only.  A step is backward, `project_grads_()`, the configured clip / scaler / grad_conditioning on the adapter
         gradients, the optimizer step, `merge_()`; before every step the trainer re-merges if `lora.merged()` is False.
         `save_checkpoint` / `load_checkpoint` write and read `<output>/lora/<step>.pth` in place of the base checkpoint.
-        ValueError with ddp=True and with graph=True, NotImplementedError with the SD 2.1 UNet."""
+        ValueError with ddp=True and with graph=True, NotImplementedError with the SD 2.1 UNet.
+        ema (MMDiT and UNet, every mode above): None (default) = no average, every launch as before.  A dict of
+        train.EMA's keyword arguments (decay, min_decay, update_after_step, use_ema_warmup, inv_gamma, power: diffusers' EMAModel)
+        or a train.EMA = an exponential moving average of the optimized parameters (with `lora` the adapter tensors), one fp32
+        shadow each, moved inside the AdamW kernels of every optimizing call (so once per gradient-accumulation cycle; in graph mode
+        without a host read: the decay rides in the optimizer's hyper row).  A step skipped for non-finite gradients advances
+        `ema.optimization_step` and leaves the shadows alone.  `with trainer.ema_weights():` evaluates with the averaged weights
+        (an in-place exchange: no third copy, no graph recapture); `train_step` inside it raises RuntimeError.  `save_checkpoint`
+        also writes `<output>/ema/<step>.pth`, `load_checkpoint` reads it - or, where it is absent (resuming a run that had no
+        EMA), restarts the shadows from the loaded parameters with one warning."""
         from . import train as _train
         from .unet import UNetCrossviewTemporalConditionModel
         if activations not in _train.ACTIVATION_POLICIES:
@@ -627,6 +637,11 @@ class CTSDTrainer:
         opt_cls = _train.AdamW8bit if optimizer_bits == 8 else _train.AdamW
         self.optimizer = opt_cls(self._optimized(), lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         self.lr_scheduler = lr_scheduler(self.optimizer) if callable(lr_scheduler) else lr_scheduler
+        self.ema = None
+        if ema is not None:                         # over what the optimizer steps, under the names of the checkpoint it belongs to
+            if not isinstance(ema, (dict, _train.EMA)):
+                raise TypeError(f"CTSDTrainer(ema=...): None, a dict of train.EMA's keyword arguments or a train.EMA, got {type(ema)}")
+            self.ema = ema if isinstance(ema, _train.EMA) else _train.EMA(self._named_optimized(), **ema)
         self.global_step = 0
         self.sigmas = flow_match_train_sigmas(num_train_timesteps, shift)
         self.num_train_timesteps, self.loss_coef = num_train_timesteps, loss_coef
@@ -661,6 +676,38 @@ class CTSDTrainer:
         """the parameters the optimizer steps and the clip reads: the model's, or with adapters theirs"""
         lora = getattr(self, "lora", None)
         return list(self.model.parameters() if lora is None else lora.parameters())
+
+    def _named_optimized(self) -> list:
+        """`_optimized()` as (state-dict key, parameter) pairs: the keys of the model's checkpoint, or with adapters of theirs"""
+        lora = getattr(self, "lora", None)
+        names = {id(v): k for k, v in (self.model if lora is None else lora).state_dict(keep_vars=True).items()}
+        return [(names.get(id(p), str(i)), p) for i, p in enumerate(self._optimized())]
+
+    # ---- EMA of the weights (DESIGN §27)
+    def _ema_exchange(self) -> None:
+        """parameters <-> shadows, then everything derived from the old values goes: train.EMA.swap_ rewrites the compute copies that
+        blocks.STORE refreshes in place and forgets the others, the model's caches are dropped here, and with adapters the targets'
+        compute copies are merged again from the tensors that are the adapters now"""
+        from .blocks import drop_caches
+        self.ema.swap_()
+        drop_caches(self.model)
+        if getattr(self, "lora", None) is not None:
+            self.lora.merge_()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """`with trainer.ema_weights() as model:` - inside, the model (with adapters: their merged compute copies) holds the
+        averaged weights; on exit, exceptions included, the trained ones are back bit for bit.  No parameter, shadow or compute
+        copy changes its address, so the graph of graph mode stays valid."""
+        if getattr(self, "ema", None) is None:
+            raise RuntimeError("CTSDTrainer.ema_weights(): the trainer was built without ema=")
+        if self.ema.swapped:
+            raise RuntimeError("CTSDTrainer.ema_weights(): already inside ema_weights()")
+        self._ema_exchange()
+        try:
+            yield self.model
+        finally:
+            self._ema_exchange()
 
     @property
     def activation_plan(self):
@@ -803,6 +850,12 @@ class CTSDTrainer:
         osd = self.optimizer.state_dict()
         osd["state"] = {i: {k: (v.detach().cpu() if torch.is_tensor(v) else v) for k, v in st.items()} for i, st in osd["state"].items()}
         torch.save(osd, os.path.join(output_path, "optimizer", f"{steps}.pth"))
+        ema = getattr(self, "ema", None)
+        if ema is not None:                         # the shadows under the checkpoint's keys, the six settings and the counter
+            os.makedirs(os.path.join(output_path, "ema"), exist_ok=True)
+            esd = ema.state_dict()
+            esd["shadows"] = {k: v.cpu() for k, v in esd["shadows"].items()}
+            torch.save(esd, os.path.join(output_path, "ema", f"{steps}.pth"))
 
     def load_checkpoint(self, output_path: str, resume_from: int) -> None:
         """model + optimizer state of step `resume_from`; the call counter continues there, so the gradient-accumulation
@@ -822,28 +875,46 @@ class CTSDTrainer:
                                                   map_location="cpu", weights_only=True))
         self.optimizer.load_state_dict(torch.load(os.path.join(output_path, "optimizer", f"{resume_from}.pth"),
                                                   map_location="cpu", weights_only=True))
+        ema = getattr(self, "ema", None)
+        if ema is not None:
+            path = os.path.join(output_path, "ema", f"{resume_from}.pth")
+            if os.path.exists(path):
+                ema.load_state_dict(torch.load(path, map_location="cpu", weights_only=True))
+            else:                                   # resuming a run that had no EMA: the average starts at the loaded weights
+                import warnings
+                warnings.warn(f"CTSDTrainer.load_checkpoint: {path} is absent - the EMA shadows restart from the loaded parameters "
+                              "with optimization_step = 0")
+                ema.reset_()
 
     def _fused_optimizer_step(self, scaler) -> None:
         """the optimizing part of train_step in grad_conditioning="fused": one read of the gradients, one host sync, the AdamW
         launch with the coefficient; nothing extra when neither a clip nor a scaler is configured"""
+        ekw = self._ema_kw()
         if scaler is None and self.max_grad_norm is None:
-            self.optimizer.step()
+            self.optimizer.step(**ekw)
         else:
             from .train import grad_norm_and_coef
             inv_scale = 1.0 if scaler is None else 1.0 / scaler.get_scale()
             self.last_grad_norm, coef, found_inf = grad_norm_and_coef(self._optimized(), self.max_grad_norm, inv_scale)
             if found_inf:
                 self.skipped_steps += 1
+                if ekw:                              # the skipped call counts, the shadows stay (train.EMA)
+                    self.ema.advance()
                 if scaler is None and not self._warned_nonfinite:
                     import warnings
                     warnings.warn("CTSDTrainer(grad_conditioning='fused'): non-finite gradient without a grad scaler - the optimizer "
                                   "step is skipped (further ones silently; see skipped_steps)")
                     self._warned_nonfinite = True
             else:
-                self.optimizer.step(grad_scale=coef)
+                self.optimizer.step(grad_scale=coef, **ekw)
             if scaler is not None:
                 scaler.update(found_inf)
         self.optimizer.zero_grad()
+
+    def _ema_kw(self) -> dict:
+        """the keyword that hands the EMA to `optimizer.step`; without one the call is made as it always was"""
+        ema = getattr(self, "ema", None)
+        return {} if ema is None else {"ema": ema}
 
     # ---- whole-step HIP graph (DESIGN §25).  The captured region is `_loss_of` + backward on static copies of what `_stage_inputs`
     # makes.  A replay reads three kinds of memory only: allocations of the capture's own pool (activations, gradients, every
@@ -944,13 +1015,14 @@ class CTSDTrainer:
     def _graph_optimizer_step(self, scaler) -> None:
         from . import train_ops as _T
         from .train import _fp32_grad
+        ekw = self._ema_kw()                         # the decay is host-known (the counter advances on skipped steps too)
         if scaler is None and self.max_grad_norm is None:
-            self.optimizer.step(device_operands=(None, None))
+            self.optimizer.step(device_operands=(None, None), **ekw)
             return
         gs = [_fp32_grad(p) for p, _ in self._g_grads]
         inv_scale = 1.0 if scaler is None else 1.0 / scaler.get_scale()
         cond = _T.grad_sumsq_multi(gs, inv_scale, self.max_grad_norm, reuse_items=True)
-        self.optimizer.step(device_operands=(None, cond))
+        self.optimizer.step(device_operands=(None, cond), **ekw)
         host = torch.empty(4, dtype=torch.float32, pin_memory=True)
         host.copy_(cond, non_blocking=True)
         event = torch.cuda.Event()
@@ -1001,6 +1073,10 @@ class CTSDTrainer:
         k = self.training_config.get("gradient_accumulation_steps")
         should_optimize = k is None or (gs + 1) % k == 0                                 # :1401-1404
         scaler = getattr(self, "grad_scaler", None)
+        ema = getattr(self, "ema", None)
+        if ema is not None and ema.swapped:
+            raise RuntimeError("CTSDTrainer.train_step: inside ema_weights() the model holds the averaged weights; training on them "
+                               "would move the average into the run - leave the context first")
         if getattr(self, "graph", False) and self._g_eager_done >= self.graph_warmup:
             staged = self._stage_inputs(latents, conditions, generator, timestep_indices, noise)
             loss = self._graph_train_step(staged, self._graph_signature(staged), should_optimize, scaler)
@@ -1022,11 +1098,15 @@ class CTSDTrainer:
                 if scaler is not None:
                     scaler.unscale_(self.optimizer)                                      # :1411-1413
                 torch.nn.utils.clip_grad_norm_(self._optimized(), self.max_grad_norm)
+            ekw = self._ema_kw()
             if scaler is not None:
-                scaler.step(self.optimizer)                                              # :1426-1428 (skips on inf / nan)
+                counted = ema.optimization_step if ema is not None else 0
+                scaler.step(self.optimizer, **ekw)                                       # :1426-1428 (skips on inf / nan)
+                if ema is not None and ema.optimization_step == counted:                 # skipped: the call counts, the shadows stay
+                    ema.advance()
                 scaler.update()
             else:
-                self.optimizer.step()
+                self.optimizer.step(**ekw)
             self.optimizer.zero_grad()
         if should_optimize and lora is not None:         # the new A, B reach the next forward through the compute copies
             lora.merge_()

@@ -1128,9 +1128,14 @@ class AdamW(torch.optim.Optimizer):
         return st
 
     @torch.no_grad()
-    def step(self, closure=None, grad_scale: float = 1.0, device_operands: Optional[tuple] = None):
+    def step(self, closure=None, grad_scale: float = 1.0, device_operands: Optional[tuple] = None, ema: Optional["EMA"] = None):
         """the step of `AdamW` and of `AdamW8bit`: a parameter whose `exp_avg` is uint8 goes to the `dwm_adamw8_multi` batch of its
         step count, every other one to the `dwm_adamw_multi` batch; per group the 8-bit batches are launched first.
+        ema (an `EMA`; None: every launch as without it): its counter advances, and its shadows move with this step's decay - in the
+        same pass as the update for the parameters of a batch (`dwm_adamw_ema_multi` / `dwm_adamw8_ema_multi`; a batch without a
+        single shadow takes the plain entry), in one `dwm_ema_multi` launch for the parameters that have a shadow but no gradient in
+        this step.  With device_operands the decay travels in the fourth float of the hyper row and a set non-finite flag leaves
+        the shadows alone as well; a given `hyper` tensor then needs that fourth float filled (`train_ops.adamw_hyper`).
         device_operands = (hyper, cond): the step is queued without a host read (`dwm_adamw_multi_dev` / `dwm_adamw8_multi_dev`).
         cond: None, or the device tensor `train_ops.grad_sumsq_multi` returned - the kernels take the gradient coefficient and the
         non-finite flag from it and change nothing when the flag is set; `grad_scale` is not used.  hyper: None - lr and the bias
@@ -1144,6 +1149,11 @@ class AdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        omd, averaged = 0.0, set()              # 1 - decay of this step; data_ptr() of the parameters whose shadow moves inside a batch
+        if ema is not None:
+            if ema.swapped:
+                raise RuntimeError(f"{name}.step(ema=...): the parameters and the shadows are exchanged (EMA.swap_()); swap back first")
+            omd = ema.advance()
         for group in self.param_groups:
             if group.get("amsgrad") or group.get("maximize"):
                 raise NotImplementedError(f"{name}: amsgrad / maximize")
@@ -1174,26 +1184,47 @@ class AdamW(torch.optim.Optimizer):
                 else:
                     raise RuntimeError(f"{name}: the parameter of shape {tuple(p.shape)} or its moments are not contiguous "
                                        "(the kernels take contiguous tensors; there is no strided path)")
+                if ema is not None:             # one more list per batch: the EMA shadow of p, or None
+                    row += (ema.shadow_of(p),)
                 step = int(st["step"].item())
                 if step not in batches:
                     batches[step] = tuple([] for _ in row)
                 for lst, t in zip(batches[step], row):
                     lst.append(t)
-            launches += [(T.adamw8_multi_, lists, step, hyper) for step, lists in batches8.items()]
-            launches += [(T.adamw_multi_, lists, step, hyper) for step, lists in batches32.items()]
+            for plain, fused, batches in ((T.adamw8_multi_, T.adamw8_ema_multi_, batches8), (T.adamw_multi_, T.adamw_ema_multi_, batches32)):
+                for step, lists in batches.items():
+                    if ema is None:
+                        launches.append((plain, lists, step, hyper))
+                    elif omd == 0.0 or not ema.fused or all(e is None for e in lists[-1]):     # nothing to average inside this batch
+                        launches.append((plain, lists[:-1], step, hyper))
+                    else:
+                        averaged.update(t.data_ptr() for t, e in zip(lists[0], lists[-1]) if e is not None)
+                        launches.append((fused, lists, step, dict(hyper, one_minus_decay=omd)))
+        # shadows whose parameter is in no batch (no gradient in this step, or not this optimizer's): one launch of the average alone
+        # (`lists[0]` holds `p.data`, a fresh tensor per access: the parameters are told apart by their storage)
+        rest = []
+        if ema is not None and omd != 0.0:
+            rest = [(e, p.data) for p, e in ema.pairs() if p.data_ptr() not in averaged]
         if device_operands is None:
             for fn, lists, step, hyper in launches:
                 fn(*lists, step=step, **hyper)
-        elif launches:
+            if rest:
+                T.ema_multi_([e for e, _ in rest], [p for _, p in rest], one_minus_decay=omd)
+        elif launches or rest:
             given, cond = device_operands
-            dev = launches[0][1][0][0].device
-            if given is None:                   # one row of (lr, bias_corr1, bias_corr2, 0) per launch, one copy for all of them
-                host = torch.empty((len(launches), 4), dtype=torch.float32, pin_memory=True)
+            dev = launches[0][1][0][0].device if launches else rest[0][1].device
+            if given is None:                   # one row of (lr, bias_corr1, bias_corr2, 1 - decay) per launch, one copy for all of them
+                host = torch.empty((len(launches) + bool(rest), 4), dtype=torch.float32, pin_memory=True)
                 for row, (_, _, step, hyper) in zip(host, launches):
-                    T.adamw_hyper(hyper["lr"], hyper["beta1"], hyper["beta2"], step, out=row)
+                    T.adamw_hyper(hyper["lr"], hyper["beta1"], hyper["beta2"], step, out=row, one_minus_decay=omd)
+                if rest:
+                    host[-1].zero_()
+                    host[-1, 3] = omd
                 rows = host.to(dev, non_blocking=True)
             for i, (fn, lists, step, hyper) in enumerate(launches):
                 fn(*lists, step=step, **hyper, device_operands=(rows[i] if given is None else given, cond))
+            if rest:
+                T.ema_multi_([e for e, _ in rest], [p for _, p in rest], device_operands=(rows[-1] if given is None else given, cond))
         STORE.bump(keep_shadows=True)
         return loss
 
@@ -1273,6 +1304,157 @@ class AdamW8bit(AdamW):
                     st[key] = T.dequantize_blockwise8(st[key], st.pop(key + "_absmax"), code)
             state[i] = st
         return {"state": state, "param_groups": sd["param_groups"]}
+
+
+# ------------------------------------------------------------------------------------------ EMA of the weights
+class EMA:
+    """Exponential moving average of the trained weights with the semantics of diffusers 0.31 `EMAModel` (decay schedule and update
+    formula), kept in one fp32 shadow per parameter that `requires_grad` and moved by the optimizer's own kernels
+    (`AdamW.step(ema=...)`: `dwm_adamw_ema_multi` & co.).  Frozen parameters get no shadow: evaluating "with EMA" uses
+    their own value.
+
+    parameters: an iterable of parameters or of (name, parameter) pairs; the names key `state_dict()` (without names: "0", "1", ...).
+    Shadows start as a copy of their parameter.
+
+    The decay of the step with counter value n (`get_decay(n)`): s = max(0, n - update_after_step - 1); s <= 0: 0, else
+    1 - (1 + s / inv_gamma) ** -power with `use_ema_warmup`, (1 + s) / (10 + s) without, clamped to [min_decay, decay].  A step
+    then does  shadow += (1 - decay) * (parameter - shadow)  on the parameter the optimizer has just written.
+
+    `optimization_step` advances on every optimizing call (`advance()`, which `AdamW.step(ema=...)` calls), as diffusers' `step()`
+    does - including a call whose optimizer step was skipped for non-finite gradients.  ONE DELIBERATE DIFFERENCE from calling
+    `EMAModel.step` after a skipped optimizer step: the skipped step leaves the shadows untouched here (diffusers would average the
+    unchanged parameters in once more).  Only the counter moves, which is also what keeps the decay known on the host when the
+    skip is decided on the device (`CTSDTrainer(graph=True)`).
+
+    `swap_()` exchanges parameters and shadows in place (`dwm_ema_swap_multi`: no third copy, storage addresses unchanged, bf16
+    compute copies that blocks.STORE refreshes in place rewritten by the same kernel, the others forgotten); `swapped` tells which
+    way round they are.  `averaged_state_dict(model)` is `model.state_dict()` with the shadows substituted."""
+
+    SETTINGS = ("decay", "min_decay", "update_after_step", "use_ema_warmup", "inv_gamma", "power")
+    # True: `AdamW.step(ema=...)` moves the shadows inside the optimizer's launches.  False: the plain optimizer launches, then one
+    # `dwm_ema_multi` launch over every shadow (the same element rule on the same p') - the two-launch route that
+    # scripts/measure_ema.py times against the fused one.
+    fused = True
+
+    def __init__(self, parameters, decay: float = 0.9999, min_decay: float = 0.0, update_after_step: int = 0,
+                 use_ema_warmup: bool = False, inv_gamma: float = 1.0, power: float = 2 / 3):
+        if not 0.0 <= min_decay <= decay <= 1.0:
+            raise ValueError(f"EMA: 0 <= min_decay <= decay <= 1 expected, got min_decay={min_decay!r}, decay={decay!r}")
+        self.decay, self.min_decay, self.update_after_step = float(decay), float(min_decay), int(update_after_step)
+        self.use_ema_warmup, self.inv_gamma, self.power = bool(use_ema_warmup), float(inv_gamma), float(power)
+        self.optimization_step = 0
+        self.swapped = False
+        self._names, self._params, self._shadows = [], [], []
+        for i, item in enumerate(parameters):
+            name, p = item if isinstance(item, (tuple, list)) else (str(i), item)
+            if not p.requires_grad or any(p is q for q in self._params):
+                continue
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise ValueError(f"EMA: parameter {name!r} is {p.dtype}, contiguous={p.is_contiguous()}; fp32 contiguous master "
+                                 "parameters expected")
+            self._names.append(str(name))
+            self._params.append(p)
+            self._shadows.append(p.detach().clone())
+        self._by_id = {id(p): e for p, e in zip(self._params, self._shadows)}
+
+    def get_decay(self, optimization_step: int) -> float:
+        """the decay factor of the step that brings the counter to `optimization_step` (diffusers' EMAModel.get_decay)"""
+        step = max(0, optimization_step - self.update_after_step - 1)
+        if step <= 0:
+            return 0.0
+        if self.use_ema_warmup:
+            cur = 1 - (1 + step / self.inv_gamma) ** -self.power
+        else:
+            cur = (1 + step) / (10 + step)
+        return max(min(cur, self.decay), self.min_decay)
+
+    def advance(self) -> float:
+        """count one optimizing call and return its 1 - decay, the scalar the kernels take"""
+        self.optimization_step += 1
+        return 1.0 - self.get_decay(self.optimization_step)
+
+    def shadow_of(self, p) -> Optional[torch.Tensor]:
+        """the shadow held for the parameter `p`, or None"""
+        return self._by_id.get(id(p))
+
+    def pairs(self) -> list:
+        """[(parameter, shadow)] in the order of construction"""
+        return list(zip(self._params, self._shadows))
+
+    def named_shadows(self) -> list:
+        return list(zip(self._names, self._shadows))
+
+    @torch.no_grad()
+    def step(self) -> None:
+        """the update alone, for callers with an optimizer of their own: counts the call and averages every parameter in
+        (`dwm_ema_multi`, one launch)"""
+        if self.swapped:
+            raise RuntimeError("EMA.step: the parameters and the shadows are exchanged; swap back first")
+        omd = self.advance()
+        if omd != 0.0:
+            T.ema_multi_(self._shadows, [p.data for p in self._params], one_minus_decay=omd)
+
+    @torch.no_grad()
+    def swap_(self) -> None:
+        """parameters <-> shadows, in place; a second call restores every byte"""
+        copies = []
+        for p in self._params:
+            c = STORE.shadow_of(p) if refreshable(p) else None
+            if c is not None and (c.dtype != torch.bfloat16 or not c.is_contiguous() or c.numel() != p.numel()):
+                c = None
+            if c is None:
+                STORE.forget(p)                         # re-cast on next use
+            copies.append(c)
+        T.ema_swap_multi_([p.data for p in self._params], self._shadows, copies)
+        self.swapped = not self.swapped
+        STORE.bump(keep_shadows=True)
+
+    @torch.no_grad()
+    def reset_(self) -> None:
+        """shadows = the parameters as they are now, counter 0: the start of a run"""
+        if self.swapped:
+            raise RuntimeError("EMA.reset_: the parameters and the shadows are exchanged; swap back first")
+        for p, e in zip(self._params, self._shadows):
+            e.copy_(p.detach())
+        self.optimization_step = 0
+
+    def state_dict(self) -> dict:
+        """{"shadows": {name: tensor}, the six settings, "optimization_step"}; not while exchanged (the shadows would be the raw
+        weights)"""
+        if self.swapped:
+            raise RuntimeError("EMA.state_dict: the parameters and the shadows are exchanged; swap back first")
+        sd = {k: getattr(self, k) for k in self.SETTINGS}
+        sd["optimization_step"] = self.optimization_step
+        sd["shadows"] = {n: e.detach() for n, e in zip(self._names, self._shadows)}
+        return sd
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict: dict) -> None:
+        if self.swapped:
+            raise RuntimeError("EMA.load_state_dict: the parameters and the shadows are exchanged; swap back first")
+        shadows = state_dict["shadows"]
+        missing, unexpected = [n for n in self._names if n not in shadows], [n for n in shadows if n not in set(self._names)]
+        if missing or unexpected:
+            raise RuntimeError(f"EMA.load_state_dict: missing shadows {missing[:3]}, unexpected shadows {unexpected[:3]}")
+        for n, e in zip(self._names, self._shadows):
+            if tuple(shadows[n].shape) != tuple(e.shape):
+                raise RuntimeError(f"EMA.load_state_dict: shadow {n!r} is {tuple(shadows[n].shape)}, expected {tuple(e.shape)}")
+        for n, e in zip(self._names, self._shadows):
+            e.copy_(shadows[n])
+        self.decay, self.min_decay = float(state_dict["decay"]), float(state_dict["min_decay"])
+        self.update_after_step, self.use_ema_warmup = int(state_dict["update_after_step"]), bool(state_dict["use_ema_warmup"])
+        self.inv_gamma, self.power = float(state_dict["inv_gamma"]), float(state_dict["power"])
+        self.optimization_step = int(state_dict["optimization_step"])
+
+    def averaged_state_dict(self, model: torch.nn.Module) -> dict:
+        """`model.state_dict()` (detached tensors that share the parameters' storage) with the averaged value in place of every entry
+        that has one: what to write as an inference checkpoint, without exchanging anything.  While exchanged, the averaged values
+        are the parameters themselves."""
+        out = type(model.state_dict())()
+        for k, v in model.state_dict(keep_vars=True).items():
+            e = None if self.swapped else self._by_id.get(id(v))
+            out[k] = v.detach() if e is None else e
+        return out
 
 
 # ------------------------------------------------------------------------------------------ gradient clip / loss scale

@@ -261,8 +261,9 @@ class _BlockTables:
         return self._scratch
 
 
-# (device index, chunk, tuple of numels) -> _BlockTables, least recently used first.  Four entries: the fp32 list of an optimizer, its
-# 8-bit list, the gradient list (one entry with either where the numels are the same) and one spare.
+# (device index, chunk, tuple of numels) -> _BlockTables, least recently used first.  Six entries: the fp32 list of an optimizer, its
+# 8-bit list, the gradient list (one entry with either where the numels are the same), the two lists of an EMA (the shadows without a
+# gradient in the step, the exchange) and one spare.
 _BLOCK_TABLES: dict = {}
 
 
@@ -270,7 +271,7 @@ def _block_tables(dev: torch.device, chunk: int, numels: tuple) -> _BlockTables:
     key = (dev.index, chunk, numels)
     tab = _BLOCK_TABLES.pop(key, None)                # a hit goes back in as the most recent
     if tab is None:
-        while len(_BLOCK_TABLES) >= 4:
+        while len(_BLOCK_TABLES) >= 6:
             _BLOCK_TABLES.pop(next(iter(_BLOCK_TABLES)))
         tab = _BlockTables(dev, chunk, numels)
     _BLOCK_TABLES[key] = tab
@@ -311,25 +312,28 @@ def adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, p
           *_adamw_scalars(lr, beta1, beta2, eps, weight_decay, step, grad_scale))
 
 
-def _dev_operands(device_operands, dev: torch.device, what: str) -> tuple:
-    """(hyper, cond) of the *_dev entry points checked: hyper fp32 [>= 3] = (lr, bias_corr1, bias_corr2), cond None or fp32 [>= 3] =
-    the out of grad_sumsq_multi, both contiguous on `dev`"""
+def _dev_operands(device_operands, dev: torch.device, what: str, hyper_floats: int = 3) -> tuple:
+    """(hyper, cond) of the *_dev entry points checked: hyper fp32 [>= 3] = (lr, bias_corr1, bias_corr2) - [>= 4] with
+    one_minus_decay behind them for the EMA forms (hyper_floats) -, cond None or fp32 [>= 3] = the out of grad_sumsq_multi, both
+    contiguous on `dev`"""
     hyper, cond = device_operands
-    for t, name in ((hyper, "hyper"), (cond, "cond")):
+    for t, name, need in ((hyper, "hyper", hyper_floats), (cond, "cond", 3)):
         if t is None and name == "cond":
             continue
-        if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < 3 or t.device != dev:
-            raise RuntimeError(f"{what}: device_operands {name} must be a contiguous fp32 tensor of at least 3 elements on the "
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < need or t.device != dev:
+            raise RuntimeError(f"{what}: device_operands {name} must be a contiguous fp32 tensor of at least {need} elements on the "
                                "tensors' device")
     return hyper, cond
 
 
-def adamw_hyper(lr: float, beta1: float, beta2: float, step: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """host tensor [4] = (lr, bias_corr1, bias_corr2, 0) of one optimizer step: the `hyper` array of the *_dev entry points, from the
-    scalars `_adamw_scalars` hands the by-value ones (so a float32 of either holds the same bits)"""
+def adamw_hyper(lr: float, beta1: float, beta2: float, step: int, out: Optional[torch.Tensor] = None,
+                one_minus_decay: float = 0.0) -> torch.Tensor:
+    """host tensor [4] = (lr, bias_corr1, bias_corr2, one_minus_decay) of one optimizer step: the `hyper` array of the *_dev entry
+    points, from the scalars `_adamw_scalars` hands the by-value ones (so a float32 of either holds the same bits).  The fourth
+    float is read by the EMA forms only."""
     sc = _adamw_scalars(lr, beta1, beta2, 0.0, 0.0, step, 1.0)
     out = torch.empty(4, dtype=torch.float32) if out is None else out
-    out[0], out[1], out[2], out[3] = sc[0], sc[5], sc[6], 0.0
+    out[0], out[1], out[2], out[3] = sc[0], sc[5], sc[6], one_minus_decay
     return out
 
 
@@ -420,6 +424,133 @@ def adamw8_multi_(ps, gs, mqs, mas, vqs, vas, shadows, *, lr: float, beta1: floa
         return
     _call("dwm_adamw8_multi", _p(items), _p(tab.block_item), _p(tab.block_start), tab.block_item.numel(), ADAMW_CHUNK, _p(code_m),
           _p(code_v), *_adamw_scalars(lr, beta1, beta2, eps, weight_decay, step, grad_scale))
+
+
+# ---- EMA weights (include/dwm_hip.h "EMA weights"): e' = e + one_minus_decay * (p' - e), one fp32 shadow per tensor
+def _chk_ema(e: Optional[torch.Tensor], p: torch.Tensor, what: str) -> int:
+    """the pointer of the shadow `e` of `p` (0 for None: the tensor has none)"""
+    if e is None:
+        return 0
+    if e.dtype != torch.float32 or not e.is_contiguous() or e.numel() != p.numel() or e.device != p.device or e.data_ptr() == p.data_ptr():
+        raise RuntimeError(f"{what}: a shadow must be an fp32 contiguous tensor of its parameter's size on its device, and not the "
+                           "parameter itself")
+    return e.data_ptr()
+
+
+def _chk_omd(one_minus_decay: float, what: str) -> float:
+    if not 0.0 <= one_minus_decay <= 1.0:               # a nan fails both comparisons
+        raise ValueError(f"{what}: one_minus_decay must be in [0, 1], got {one_minus_decay!r}")
+    return float(one_minus_decay)
+
+
+def adamw_ema_multi_(ps, gs, ms, vs, shadows, emas, *, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
+                     step: int, one_minus_decay: float, grad_scale: float = 1.0, device_operands: Optional[tuple] = None) -> None:
+    """dwm_adamw_ema_multi: adamw_multi_ with the EMA shadow of every entry (emas: fp32 tensor or None = no shadow, updated as by
+    adamw_multi_) moved in the same pass.  p / m / v / the bf16 copies come out bit-equal to adamw_multi_.
+    device_operands = (hyper, cond): dwm_adamw_ema_multi_dev - as for adamw_multi_, and one_minus_decay is read from hyper[3]
+    (`adamw_hyper(..., one_minus_decay=)`); the keyword is then not used."""
+    if not ps:
+        return
+    dev = ps[0].device
+    rows = []
+    for p, g, m, v, sh, e in zip(ps, gs, ms, vs, shadows, emas):
+        for t in (p, g, m, v):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel() or t.device != dev:
+                raise RuntimeError("adamw_ema_multi_: fp32 contiguous tensors of one shape on one device expected")
+        rows.append((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), 0 if sh is None else sh.data_ptr(),
+                     _chk_ema(e, p, "adamw_ema_multi_"), p.numel()))
+    items = _items(rows, dev, reuse=device_operands is not None)                      # [n, 7] = dwm_adamw_ema_item[n]
+    tab = _block_tables(dev, ADAMW_CHUNK, tuple(r[-1] for r in rows))
+    if device_operands is not None:
+        hyper, cond = _dev_operands(device_operands, dev, "adamw_ema_multi_", hyper_floats=4)
+        _call("dwm_adamw_ema_multi_dev", _p(items), _p(tab.block_item), _p(tab.block_start), tab.block_item.numel(), ADAMW_CHUNK,
+              _p(hyper), _p(cond), beta1, beta2, eps, weight_decay)
+        return
+    _call("dwm_adamw_ema_multi", _p(items), _p(tab.block_item), _p(tab.block_start), tab.block_item.numel(), ADAMW_CHUNK,
+          *_adamw_scalars(lr, beta1, beta2, eps, weight_decay, step, grad_scale), _chk_omd(one_minus_decay, "adamw_ema_multi_"))
+
+
+def adamw8_ema_multi_(ps, gs, mqs, mas, vqs, vas, shadows, emas, *, lr: float, beta1: float, beta2: float, eps: float,
+                      weight_decay: float, step: int, one_minus_decay: float, grad_scale: float = 1.0,
+                      device_operands: Optional[tuple] = None) -> None:
+    """dwm_adamw8_ema_multi: adamw8_multi_ with the EMA shadows (fp32; None = no shadow) moved in the same pass; everything else as
+    adamw_ema_multi_"""
+    if not ps:
+        return
+    dev = ps[0].device
+    rows = []
+    for p, g, mq, ma, vq, va, sh, e in zip(ps, gs, mqs, mas, vqs, vas, shadows, emas):
+        for t in (p, g):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel() or t.device != dev:
+                raise RuntimeError("adamw8_ema_multi_: fp32 contiguous tensors of one shape on one device expected")
+        _chk_q8(mq, ma, p.numel(), dev, "adamw8_ema_multi_")
+        _chk_q8(vq, va, p.numel(), dev, "adamw8_ema_multi_")
+        rows.append((p.data_ptr(), g.data_ptr(), mq.data_ptr(), ma.data_ptr(), vq.data_ptr(), va.data_ptr(),
+                     0 if sh is None else sh.data_ptr(), _chk_ema(e, p, "adamw8_ema_multi_"), p.numel()))
+    items = _items(rows, dev, reuse=device_operands is not None)                      # [n, 9] = dwm_adamw8_ema_item[n]
+    tab = _block_tables(dev, ADAMW_CHUNK, tuple(r[-1] for r in rows))
+    code_m, code_v = quant8.device_codes(dev)
+    if device_operands is not None:
+        hyper, cond = _dev_operands(device_operands, dev, "adamw8_ema_multi_", hyper_floats=4)
+        _call("dwm_adamw8_ema_multi_dev", _p(items), _p(tab.block_item), _p(tab.block_start), tab.block_item.numel(), ADAMW_CHUNK,
+              _p(code_m), _p(code_v), _p(hyper), _p(cond), beta1, beta2, eps, weight_decay)
+        return
+    _call("dwm_adamw8_ema_multi", _p(items), _p(tab.block_item), _p(tab.block_start), tab.block_item.numel(), ADAMW_CHUNK, _p(code_m),
+          _p(code_v), *_adamw_scalars(lr, beta1, beta2, eps, weight_decay, step, grad_scale),
+          _chk_omd(one_minus_decay, "adamw8_ema_multi_"))
+
+
+def ema_multi_(emas, ps, *, one_minus_decay: float = 0.0, device_operands: Optional[tuple] = None) -> None:
+    """dwm_ema_multi: emas[i] += one_minus_decay * (ps[i] - emas[i]) for the whole list in one launch; ps are read only.
+    device_operands = (hyper, cond), either may be None: hyper (device fp32 [>= 4]) - one_minus_decay is read from hyper[3] and the
+    keyword is not used; cond (device fp32 [>= 3], the out of grad_sumsq_multi) - nothing changes when cond[2] is set."""
+    if not ps:
+        return
+    dev = ps[0].device
+    rows = []
+    for e, p in zip(emas, ps):
+        if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev or not p.is_cuda or e is None:
+            raise RuntimeError("ema_multi_: fp32 contiguous parameters with a shadow each on one HIP device expected (there is no "
+                               "CPU fallback)")
+        if p.numel() > 0:
+            rows.append((_chk_ema(e, p, "ema_multi_"), p.data_ptr(), p.numel()))
+    if not rows:
+        return
+    hyper = cond = None
+    if device_operands is not None:
+        hyper, cond = device_operands
+        for t, name, need in ((hyper, "hyper", 4), (cond, "cond", 3)):
+            if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < need
+                                  or t.device != dev):
+                raise RuntimeError(f"ema_multi_: device_operands {name} must be None or a contiguous fp32 tensor of at least {need} "
+                                   "elements on the tensors' device")
+    items = _items(rows, dev, reuse=device_operands is not None)                      # [n, 3] = dwm_ema_item[n]
+    tab = _block_tables(dev, ADAMW_CHUNK, tuple(r[-1] for r in rows))
+    omd = 0.0 if hyper is not None else _chk_omd(one_minus_decay, "ema_multi_")
+    _call("dwm_ema_multi", _p(items), _p(tab.block_item), _p(tab.block_start), tab.block_item.numel(), ADAMW_CHUNK, omd, _p(hyper),
+          _p(cond))
+
+
+def ema_swap_multi_(ps, emas, shadows) -> None:
+    """dwm_ema_swap_multi: ps[i] <-> emas[i] in place for the whole list in one launch; shadows[i] (bf16 compute copy or None)
+    receives the bf16 of the new ps[i].  A second call restores every byte."""
+    if not ps:
+        return
+    dev = ps[0].device
+    rows = []
+    for p, e, sh in zip(ps, emas, shadows):
+        if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev or not p.is_cuda or e is None:
+            raise RuntimeError("ema_swap_multi_: fp32 contiguous parameters with a shadow each on one HIP device expected (there is "
+                               "no CPU fallback)")
+        if sh is not None and (sh.dtype != bf16 or not sh.is_contiguous() or sh.numel() != p.numel() or sh.device != dev):
+            raise RuntimeError("ema_swap_multi_: a compute copy must be a contiguous bf16 tensor of its parameter's size")
+        if p.numel() > 0:
+            rows.append((p.data_ptr(), _chk_ema(e, p, "ema_swap_multi_"), 0 if sh is None else sh.data_ptr(), p.numel()))
+    if not rows:
+        return
+    items = _items(rows, dev, reuse=True)                                             # [n, 4] = dwm_ema_swap_item[n]
+    tab = _block_tables(dev, ADAMW_CHUNK, tuple(r[-1] for r in rows))
+    _call("dwm_ema_swap_multi", _p(items), _p(tab.block_item), _p(tab.block_start), tab.block_item.numel(), ADAMW_CHUNK)
 
 
 # ---- gradient norm / clip coefficient / non-finite check in one read (gradnorm.hip)
